@@ -1,6 +1,14 @@
 """Benchmark of the MI355X pose-lifting MLP (BASELINE.json metric: poses/s at batch 64).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--mode infer|train|eval|stress|data]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what its headline figure needs and nothing else: set up, warm up, time the K
+steps, write the outputs of the timed path (--dump-outputs DIR: DIR/<name>.npy, what the last
+timed pass left in the arrays a caller receives; the inputs are seeded, so two builds can be
+compared output for output) and print the result line.  --full adds everything else described
+below: the sub-measurements beside the default infer line, the live-timed `roofline` of the
+dominant kernel and the host `cpu_baseline`.
 
 Modes (BASELINE.json configs):
   infer  (default, configs[1]) L=1024, 2 residual blocks, BN, batch 64, fp32 inference.
@@ -23,7 +31,7 @@ Modes (BASELINE.json configs):
 
 Multi-GPU: one process per GPU (torch.distributed.run); inference shards by batch
 with no data-path collective (scaling "weak"); train is data parallel (RCCL).
-Rank 0 prints ONE JSON line.  Alongside `value` it reports `roofline` (dominant
+Rank 0 prints ONE JSON line.  With --full it reports, alongside `value`, `roofline` (dominant
 kernel timed live with hipEvent pairs, see p3d_profile_*) and `cpu_baseline`
 (the numpy fp32 restatement of the TF1 path, oracle/ref_mlp.py, on the host).
 """
@@ -49,6 +57,33 @@ L, NBLK, IN, OUT, BATCH = 1024, 2, 32, 48, 64
 def flops_per_pose(L=L, N=NBLK):
     """2*(32L + 2N*L^2 + 48L) GEMM FLOP per pose (forward)."""
     return 2 * (IN * L + 2 * N * L * L + OUT * L)
+
+
+DUMP_BYTES = 60 * 1000 * 1000   # --dump-outputs: all files together stay under 64 MB
+
+
+def dump_outputs(args, rank, **arrays):
+    """--dump-outputs DIR: rank 0 writes each device tensor / array as DIR/<name>.npy (float32 or
+    float64).  An array over its share of DUMP_BYTES is cut to a fixed sample of its leading
+    axis (seed 0, sorted indices), the same sample in every run of the same arguments.  The
+    first call writes (the headline path's); the option is cleared so that no later
+    measurement of the same run overwrites the files."""
+    d, args.dump_outputs = args.dump_outputs, None
+    if not d or rank != 0:
+        return
+    import torch
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, a in arrays.items():
+        if not isinstance(a, torch.Tensor):
+            a = torch.from_numpy(np.ascontiguousarray(a))
+        if a.dtype not in (torch.float32, torch.float64):
+            a = a.to(torch.float64)
+        row = a[0].numel() * a.element_size() if a.dim() else 0
+        if a.dim() and a.shape[0] * row > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.shape[0], max(1, share // row), replace=False))
+            a = a.index_select(0, torch.from_numpy(keep).to(a.device))
+        np.save(os.path.join(d, name + ".npy"), a.detach().cpu().numpy())
 
 
 def _free_port():
@@ -406,6 +441,10 @@ def bench_serve(args, rank, world):
     dt = sorted(samples)[len(samples) // 2]
     model.serve_check()
     value = world * args.steps * BATCH / dt
+    dump_outputs(args, rank, y=Y)     # [K, 64, 48]: every timed step's batch, as the last repeat wrote it
+    if not args.full:
+        model.close()
+        return value, dt, {"steps_per_launch": C}
     # where the wall time of a launch goes (diagnostic, untimed): host enqueue of one launch,
     # one launch + synchronize round trip, synchronize of an idle device (medians)
     import torch
@@ -735,6 +774,10 @@ def bench_train(args, rank, world, steps=None, warmup=None, bucket_mb=None, dp=N
     barrier_sync(world)
     dt = max_over_ranks(time.perf_counter() - t0, world)
     value = world * steps * BATCH / dt
+    dump_outputs(args, rank, y=Y)     # the last timed step's outputs [64, 48]
+    if not args.full:
+        model.close()
+        return value, dt, None, mode
     prof = profile_kernels(model, lambda: run(min(steps, 32)))
     # dominant HBM kernel: fused Adam + re-pack over the 4,291,632 trainables:
     # p, m, v read+write, g read (7 x 4 B) + Wf, Wd written (2 x 4 B per weight element)
@@ -847,10 +890,11 @@ def bench_eval(args, rank, world):
     frames = sum(nb) * BATCH
     assert int(round(t[:, 17].sum())) == frames, (t[:, 17].sum(), frames)
     errs = t[:, :17].sum(1) / (t[:, 17] * 17)
+    dump_outputs(args, rank, per_action_table=t)   # [15, 19] fp64: joint sums, frames, loss sum
     # dominant kernel of the sweep: the large-M hidden layers (k_gemm_f32) of one whole
     # sweep, each launch timed with dispatch-attached events; FLOPs from the chunk sizes
     big_m = int(os.environ.get("P3D_BIG_M", "256"))
-    prof = profile_kernels(model, sweep)
+    prof = profile_kernels(model, sweep) if args.full else {}
     big_rows = 0
     for r in rows:
         for s0 in range(0, r, chunk):
@@ -1038,6 +1082,10 @@ def bench_stress(args, rank, world, steps=None, warmup=None):
     barrier_sync(world)
     dt = max_over_ranks(time.perf_counter() - t0, world)
     value = world * steps * Bs / dt
+    dump_outputs(args, rank, y=Y)     # [8, 1024, 48]: the graph's 8 batches, as the last replay wrote them
+    if not args.full:
+        model.close()
+        return value, dt, None, steps
     # hidden-layer launches of 8 steps in step order (32 MB of bf16 weights per layer,
     # rotating), dispatch-attached events; isolated: one layer relaunched with hot weights
     prof = profile_kernels(model, lambda: run(G))
@@ -1121,13 +1169,21 @@ def bench_data(args, rank, world):
         step()
     barrier_sync(world)
     dt = max_over_ranks(time.perf_counter() - t0, world) / reps
+    F2 = S * 4 * frames
+    if args.dump_outputs:
+        n2, n3 = step()
+        dump_outputs(args, rank, norm2d=n2, norm3d=n3)
+    if not args.full:
+        return {"workload": "H3.6M train-set preprocessing (create_2d_data + read_3d_data numerics), "
+                            "%d world frames x 4 cameras, float64" % (S * frames),
+                "value": round(F2 / dt, 1), "unit": "camera-poses/s", "ms_per_pass": round(1000.0 * dt, 3),
+                "reps": reps, "roofline": None}
     # stage timing (one instrumented pass): which kernel dominates
     ev = {k: [] for k in ("project0", "project1", "moments2_0", "moments2_1", "normalize2_0", "normalize2_1",
                           "transform0", "transform1", "moments3_0", "moments3_1")}
     step()
     torch.cuda.synchronize()
     ms = lambda a, b: ev[a][0].elapsed_time(ev[b][0])   # noqa: E731
-    F2 = S * 4 * frames
     stages = {
         # algorithmic bytes: inputs read once, outputs written once
         "k_cam_points<2> (project, 5 launches)": (ms("project0", "project1"), S * (n * 24 + 4 * n * 16)),
@@ -1153,7 +1209,7 @@ def bench_data(args, rank, world):
                         "frac": round(ach / 8000.0, 4), "traffic": traffic, "kernel": name,
                         "bytes_per_launch": int(nbytes), "avg_us": round(1000.0 * t_ms, 2),
                         "stages_ms": {k: round(v[0], 4) for k, v in stages.items()}}}
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and not args.no_cpu:    # (--full only: a plain run returned above)
         out["cpu_baseline"] = cpu_data_baseline(args.cpu_seconds / 2)
     return out
 
@@ -1198,7 +1254,7 @@ def run_dp1_child(args, timeout=300):
     """Run the 1-rank data-parallel train leg as `bench.py --dp1-child` (a fresh process; the
     caller has not initialised the GPU) and return its JSON, or {"error": ...}."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--dp1-child", "--train-steps", str(args.train_steps),
+    cmd = [sys.executable, os.path.abspath(__file__), "--dp1-child", "--full", "--train-steps", str(args.train_steps),
            "--keep", str(args.keep)]
     if args.dp_bucket_mb is not None:
         cmd += ["--dp-bucket-mb", str(args.dp_bucket_mb)]
@@ -1277,6 +1333,11 @@ def build_arg_parser():
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--mode", choices=["infer", "train", "eval", "stress", "data"], default="infer")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the sub-measurements of infer mode, the live-timed "
+                         "roofline of the dominant kernel, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the timed path's outputs as DIR/<name>.npy")
     ap.add_argument("--graph-steps", type=int, default=240)
     ap.add_argument("--launch-steps", type=int, default=1000, help="batch-64 steps per persistent p3d_serve launch")
     ap.add_argument("--no-streams", action="store_true", help="skip the per-step kernel-chain sub-measurement")
@@ -1331,7 +1392,7 @@ def main():
     # child process that runs BEFORE this one touches the GPU: whatever happens to it (a fault, an
     # abort from a runtime thread) cannot take the headline line with it
     dp1 = None
-    if (args.mode == "infer" and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_dp1
+    if (args.full and args.mode == "infer" and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_dp1
             and args.train_steps > 0):
         dp1 = run_dp1_child(args)
     rank, world, local = setup_dist()
@@ -1341,11 +1402,17 @@ def main():
         value, dt, roof = bench_serve(args, rank, world)
         workload = ("cfg2 inference: L=1024, 2 residual blocks, BN(eval), keep=1; a step = one batch-64 request "
                     "(its own 64 poses); %d requests per persistent p3d_serve launch (%d rows, whole network "
-                    "per XCD); one request alone: latency_b64" % (roof["steps_per_launch"], 64 * roof["steps_per_launch"]))
-        try:
-            lat = bench_latency_b64()
-        except Exception as exc:
-            lat = {"error": repr(exc)[:300]}
+                    "per XCD)%s" % (roof["steps_per_launch"], 64 * roof["steps_per_launch"],
+                                    "; one request alone: latency_b64" if args.full else ""))
+        if not args.full:      # a plain run: the headline alone
+            roof = None
+            args.no_streams = args.no_eval = args.no_api = args.no_data = args.no_stress = True
+            args.train_steps = 0
+        else:
+            try:
+                lat = bench_latency_b64()
+            except Exception as exc:
+                lat = {"error": repr(exc)[:300]}
         if not args.no_streams:   # the per-step kernel chain (six launches per step), 4 streams
             try:
                 cv, cdt, croof, single = bench_infer(args, rank, world)
@@ -1423,11 +1490,11 @@ def main():
     if rank == 0:
         if args.mode == "data":
             cpu = data.pop("cpu_baseline", None)
-        elif args.mode == "stress" or args.no_cpu:
+        elif args.mode == "stress" or args.no_cpu or not args.full:
             cpu = None
         else:
             cpu = cpu_baseline(args.mode, args.cpu_seconds)
-        cfg1 = bench_cfg1() if (args.mode == "infer" and not args.no_cpu and world == 1) else None
+        cfg1 = bench_cfg1() if (args.full and args.mode == "infer" and not args.no_cpu and world == 1) else None
         metric = {"stress": "poses/sec at batch 1024 (cfg5 bf16 stress)",
                   "eval": "frames/sec, evaluateActionWise MPJPE sweep (cfg4)",
                   "data": "camera-poses/sec, H3.6M train-set preprocessing (float64)"}.get(

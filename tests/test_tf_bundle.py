@@ -51,7 +51,7 @@ def _trailer(contents):
     return b"\x00" + struct.pack("<I", tb.mask(tb.crc32c(contents + b"\x00")))
 
 
-def test_read_hand_assembled_table():
+def test_read_hand_assembled_table(tmp_path):
     # one data block: "" -> "h", "ab" -> "1", "ac" -> "22" (prefix-shared), restarts [0]
     data = _block([(0, b"", b"h"), (0, b"ab", b"1"), (1, b"ac", b"22")], [0])
     meta = _block([], [0])
@@ -62,7 +62,7 @@ def test_read_hand_assembled_table():
     index = _block([(0, b"ac", bytes([0, len(data)]))], [0])        # handle: varint offset, size
     f += index + _trailer(index)
     footer = bytes([moff, len(meta), ioff, len(index)]).ljust(40, b"\x00") + struct.pack("<Q", tb.TABLE_MAGIC)
-    path = os.path.join(os.environ.get("TMPDIR", "/tmp"), "p3d_hand.index")
+    path = str(tmp_path / "p3d_hand.index")     # (a fixed name under /tmp may belong to another user)
     with open(path, "wb") as fh:
         fh.write(f + footer)
     assert tb.read_table(path) == {b"": b"h", b"ab": b"1", b"ac": b"22"}

@@ -15,7 +15,7 @@ import bench  # noqa: E402
 
 def main():
     steps = int(sys.argv[1]) if len(sys.argv) > 1 else 320
-    args = bench.build_arg_parser().parse_args([])
+    args = bench.build_arg_parser().parse_args(["--full"])   # bench_train's event-pair figures
     own = bench.init_world1_group()
     v, dt, roof, mode = bench.bench_train(args, 0, 1, steps=steps, warmup=64, dp=False)
     print(json.dumps({"form": "fused single-GPU", "us_per_step": round(1e6 * dt / steps, 2), "mode": mode,

@@ -1,12 +1,12 @@
 """Dev tool: the serve-only bench line under the library P3D_LIB names (tools/lib_ab.py runs it
-alternately for two builds): bench.py --steps 20 with every sub-measurement but the serve launch
+alternately for two builds): bench.py --steps 20 --full with every sub-measurement but the serve launch
 and the lone batch-64 request switched off."""
 import os
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-streams",
+cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-streams",
        "--no-eval", "--no-data", "--no-api", "--no-stress", "--train-steps", "0", "--no-cpu", "--no-dp1"] + sys.argv[1:]
 r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
 import json  # noqa: E402

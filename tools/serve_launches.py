@@ -1,5 +1,5 @@
 """Durations of the headline's persistent serve launches in a rocprofv3 --kernel-trace CSV of
-`bench.py --gpus 1 --steps 20 --warmup 5` (tools/profile_driver.sh), in bench_serve's launch order,
+`bench.py --gpus 1 --steps 20 --warmup 5 --full` (tools/profile_driver.sh), in bench_serve's launch order,
 next to what the bench measured with its own dispatch-attached events in the same run:
 
     python tools/serve_launches.py <trace dir> <bench_under_rocprof.json> > profiles/rNN_serve_launches.json
@@ -34,7 +34,7 @@ def main():
     i_paired = i_timed + 9 + 30 + 30 + 3
     acc = roof["host_us"].get("accounting", {}).get("serve_paired", {})
     timed, paired = dur[i_timed:i_timed + 9], dur[i_paired:i_paired + 9]
-    out = {"command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-dp1",
+    out = {"command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-dp1",
            "kernel": sorted({r["Kernel_Name"] for r in rows}), "launches": len(dur),
            "timed_repeats_us": timed, "timed_repeats_median_us": med(timed),
            "paired_repeats_us": paired, "paired_repeats_median_us": med(paired),

@@ -6,7 +6,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--mode", "train", "--steps", "400", "--warmup", "64",
-       "--no-cpu"] + sys.argv[1:]
+       "--full", "--no-cpu"] + sys.argv[1:]
 r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
 d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
 ro = d["roofline"]
