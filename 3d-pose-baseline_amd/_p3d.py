@@ -99,6 +99,16 @@ SIGNATURES = [
                            c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     ("p3d_lift_sync", c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
                                 c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    ("p3d_clip_chunk", c_int32, []),
+    ("p3d_clip_workspace", c_int64, [c_int64]),
+    ("p3d_clip_prepare", c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+                                   c_void_p, c_void_p, c_int64, c_void_p]),
+    ("p3d_clip_finish", c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                  c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    ("p3d_clip_lift_workspace", c_int64, [c_int64, c_int32, c_int32]),
+    ("p3d_clip_lift", c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
+                                c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_int64, c_void_p]),
     ("p3d_moments_workspace", c_int64, [c_int64, c_int32]),
     ("p3d_moments", c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     ("p3d_crc32c", c_uint32, [c_void_p, c_int64, c_uint32]),

@@ -9,12 +9,20 @@ the 64-wide H3.6M 2D vector (``order`` of :25 plus the derived Hip / Neck-Nose /
 of the mapped frame(s) -> ``p3d_lift`` (normalise, the float32 placeholder cast, the forward,
 unNormalizeData: one persistent launch at batch <= 4, else ``p3d_normalize`` + the layer kernels +
 ``p3d_unnormalize``, the same bits) -> pinned D2H of the [B, 96] millimetre pose(s).  The mapping is
-a host-side index shuffle of the OpenPose JSON values (as in the reference).  The plotting,
-axis swap and Maya export that follow in the sandbox are out of scope.
+a host-side index shuffle of the OpenPose JSON values (as in the reference).
+
+``ClipLifter`` lifts a whole clip -- the sandbox's own workflow (:39-227, 317-433) -- in one
+``p3d_clip_lift``: the median smoothing and the hold of dropped joints, the mapping, the forward
+in tiles of ``max_batch`` rows, the axis swap / flip / spine offset and ``--cache_on_fail``, from
+pinned rows in to pinned rows out.  ``read_openpose_json`` parses the frame files and
+``export_maya`` writes ``3d_data.json`` / ``2d_data.json``.  The plots, ``--interpolation`` and
+``--write_gif`` stay out of scope.
 """
 from __future__ import annotations
 
+import json
 import os
+import re
 
 import numpy as np
 
@@ -151,3 +159,153 @@ class FrameLifter:
         if e.shape[0] <= self.B:          # (the sandbox's per-frame call: one batch)
             return self.lift_mapped(e)
         return np.concatenate([self.lift_mapped(e[i:i + self.B]) for i in range(0, e.shape[0], self.B)])
+
+
+# --------------------------------------------------------------------------------------
+# a whole clip: src/openpose_3dpose_sandbox.py:39-227 (reading, smoothing), :317-433 (lifting, export)
+# --------------------------------------------------------------------------------------
+
+
+def parse_keypoints(data):
+    """One person's OpenPose keypoint list -> the 36 COCO-18 x/y values (:58-124): lists of >= 53
+    values carry confidences (x, y of every triple kept); more than 54 values is body_25, whose
+    joints 0-7 and 9-18 are the COCO ones; anything shorter is tf-pose-estimation's plain x/y."""
+    n = len(data)
+    xy = [data[o + k] for o in range(0, n - 1, 3) for k in (0, 1)] if n >= 53 else list(data)
+    if n > 54:
+        xy = xy[0:16] + xy[18:38]
+    return xy
+
+
+def read_openpose_json(directory):
+    """The frame files of `directory` (*.json, sorted by name) -> (frame_numbers [N] int64,
+    xy [N, 36] float64), first person of each file, key ``pose_keypoints_2d`` or
+    ``pose_keypoints``; the frame number is the last run of digits of the file name (:46-127)."""
+    names = sorted(f for f in os.listdir(directory) if f.endswith(".json"))
+    if not names:
+        raise ValueError("no .json frame files in %s" % directory)
+    numbers, rows = [], []
+    for name in names:
+        digits = re.findall(r"(\d+)", name)
+        if not digits:
+            raise ValueError("no frame number in file name %s" % name)
+        with open(os.path.join(directory, name)) as f:
+            person = json.load(f)["people"][0]
+        xy = parse_keypoints(person["pose_keypoints_2d"] if "pose_keypoints_2d" in person else person["pose_keypoints"])
+        if len(xy) != 36:
+            raise ValueError("%s: expected 18 joints (36 values), got %d values" % (name, len(xy)))
+        numbers.append(int(digits[-1]))
+        rows.append(xy)
+    return np.array(numbers, np.int64), np.array(rows, np.float64)
+
+
+def check_clip(frame_numbers, smooth=True):
+    """The conditions under which the reference's smoothing runs (:140-173): one frame, or at
+    least 9 with contiguous numbers (it indexes frame +- k and raises KeyError on a gap)."""
+    fn = np.asarray(frame_numbers, np.int64)
+    if not smooth or fn.shape[0] == 1:
+        return
+    if fn.shape[0] <= 8:
+        raise ValueError("need more frames, min 9 frames/json files for smoothing")
+    if np.any(np.diff(fn) != 1):
+        raise ValueError("frame numbers must be contiguous for smoothing (a gap after frame %d)"
+                         % fn[:-1][np.diff(fn) != 1][0])
+
+
+def export_maya(out_dir, frame_numbers, poses, xy_s):
+    """Write ``3d_data.json`` ({frame: {joint: {"translate": [x, y, z]}}}, 32 joints) and
+    ``2d_data.json`` (the 18 smoothed 2D joints, [x, y]) into `out_dir` (:326-328, 406-408, 426-433).
+    Returns the two paths."""
+    poses, xy_s = np.asarray(poses, np.float64), np.asarray(xy_s, np.float64)
+    if poses.ndim != 2 or poses.shape[1] != 96 or xy_s.shape != (poses.shape[0], 36) or len(frame_numbers) != poses.shape[0]:
+        raise ValueError("expected poses [N, 96], xy_s [N, 36] and N frame numbers")
+    three, two = {}, {}
+    for n, frame in enumerate(frame_numbers):
+        p, q = poses[n].tolist(), xy_s[n].tolist()
+        three[int(frame)] = {j: {"translate": p[3 * j:3 * j + 3]} for j in range(32)}
+        two[int(frame)] = {j: {"translate": q[2 * j:2 * j + 2]} for j in range(18)}
+    os.makedirs(out_dir, exist_ok=True)
+    paths = os.path.join(out_dir, "3d_data.json"), os.path.join(out_dir, "2d_data.json")
+    for path, units in zip(paths, (three, two)):
+        with open(path, "w") as f:
+            json.dump(units, f)
+    return paths
+
+
+class ClipLifter:
+    """Lift whole OpenPose clips of up to `max_frames` frames with a float32 LinearModel: pinned
+    rows in, ONE p3d_clip_lift (smoothing, mapping, forward tiles, post-processing), pinned rows
+    out."""
+
+    def __init__(self, model, data_mean_2d, data_std_2d, dim_to_use_2d, data_mean_3d, data_std_3d,
+                 dim_to_ignore_3d, max_frames, cache_on_fail=True):
+        import torch
+        import _p3d
+        self.torch, self.model, self.max_frames = torch, model, int(max_frames)
+        self.cache_on_fail = bool(cache_on_fail)
+        if model.bf16:
+            raise ValueError("ClipLifter: float32 models only")
+        if not 1 <= self.max_frames <= 1 << 20:
+            raise ValueError("max_frames must be in [1, 2^20]")
+        D3 = int(np.asarray(data_mean_3d).shape[0])
+        use3 = np.setdiff1d(np.arange(D3), np.asarray(dim_to_ignore_3d, np.int64))
+        if D3 != 96 or np.asarray(data_mean_2d).shape[0] != 64:
+            raise ValueError("ClipLifter: needs the 64-wide 2D and 96-wide 3D statistics")
+        if len(use3) != model.output_size or len(dim_to_use_2d) != model.input_size:
+            raise ValueError("statistics do not match the model's %d inputs / %d outputs"
+                             % (model.input_size, model.output_size))
+        dev, n = model.device, self.max_frames
+        with torch.cuda.device(dev):
+            self.m2, self.s2 = dp.as_device(data_mean_2d), dp.as_device(data_std_2d)
+            self.m3, self.s3 = dp.as_device(data_mean_3d), dp.as_device(data_std_3d)
+            self.u2 = dp._dims(dim_to_use_2d, 64, "ClipLifter")
+            self.u3 = dp._dims(use3, D3, "ClipLifter")
+            f64 = torch.float64
+            self.hin = torch.empty((n, 36), dtype=f64, pin_memory=True)
+            self.hxy = torch.empty((n, 36), dtype=f64, pin_memory=True)
+            self.hout = torch.empty((n, 96), dtype=f64, pin_memory=True)
+            self.hsrc = torch.empty((n,), dtype=torch.int32, pin_memory=True)
+            self.din = torch.empty((n, 36), dtype=f64, device=dev)
+            self.dxy = torch.empty((n, 36), dtype=f64, device=dev)
+            self.dout = torch.empty((n, 96), dtype=f64, device=dev)
+            self.dsrc = torch.empty((n,), dtype=torch.int32, device=dev)
+            self.work_bytes = int(_p3d.lib().p3d_clip_lift_workspace(n, model.input_size, model.output_size))
+            self.work = torch.empty((self.work_bytes + 256,), dtype=torch.uint8, device=dev)
+        self.work_ptr = (self.work.data_ptr() + 255) // 256 * 256
+
+    def lift_device(self, n, smooth=True):
+        """p3d_clip_lift of the first n rows of self.din into self.dxy / dout / dsrc (current stream)."""
+        import _p3d
+        p = lambda t: t.data_ptr()   # noqa: E731
+        _p3d.check(_p3d.lib().p3d_clip_lift(
+            self.model._h, p(self.din), n, int(bool(smooth)), p(self.m2), p(self.s2), p(self.u2), self.u2.numel(),
+            p(self.m3), p(self.s3), p(self.u3), self.u3.numel(), 96, int(self.cache_on_fail), p(self.dxy),
+            p(self.dout), p(self.dsrc), self.work_ptr, self.work_bytes, self.model.stream()), "p3d_clip_lift")
+
+    def network_rows(self, n):
+        """View of the network's normalised outputs [n, output_size] float32 that the last
+        lift of n frames left in the workspace (behind the scan's summaries and the input rows)."""
+        import _p3d
+        a256 = lambda b: (b + 255) // 256 * 256   # noqa: E731
+        off = int(_p3d.lib().p3d_clip_workspace(n)) + a256(n * self.model.input_size * 4)
+        return _p3d.device_view(self.work_ptr + off, (n, self.model.output_size), self.model.device.index)
+
+    def lift_clip(self, xy, smooth=True):
+        """xy [N <= max_frames, 36] raw keypoints in position order -> (poses [N, 96] float64 mm,
+        xy_s [N, 36] float64, src [N] int32: the position each exported pose came from, -1 zeros)."""
+        xy = np.asarray(xy, np.float64)
+        if xy.ndim != 2 or xy.shape[1] != 36 or not 1 <= xy.shape[0] <= self.max_frames:
+            raise ValueError("expected [1..%d, 36] keypoint rows, got %s" % (self.max_frames, xy.shape))
+        n = xy.shape[0]
+        if smooth and 2 <= n <= 8:
+            raise ValueError("need more frames, min 9 frames for smoothing")
+        self.hin.numpy()[:n] = xy
+        with self.torch.cuda.device(self.model.device):
+            self.din[:n].copy_(self.hin[:n], non_blocking=True)
+            self.lift_device(n, smooth)
+            self.hxy[:n].copy_(self.dxy[:n], non_blocking=True)
+            self.hout[:n].copy_(self.dout[:n], non_blocking=True)
+            self.hsrc[:n].copy_(self.dsrc[:n], non_blocking=True)
+            self.torch.cuda.current_stream(self.model.device).synchronize()
+        self.model.check_errors()
+        return self.hout.numpy()[:n].copy(), self.hxy.numpy()[:n].copy(), self.hsrc.numpy()[:n].copy()

@@ -415,6 +415,58 @@ int p3d_lift_sync(p3d_model* m, const double* raw, int64_t B, int32_t D2, const 
                   const int32_t* use2, int32_t U2, const double* mean3, const double* std3, const int32_t* use3,
                   int32_t U3, int32_t D3, double* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * A whole OpenPose clip (src/openpose_3dpose_sandbox.py): raw keypoints [N, 36] float64 (18 joints,
+ * x / y interleaved, rows in the order of the sorted file names) to the arrays the sandbox
+ * exports.  All arithmetic float64 in the reference's operation order, bit for bit.  1 <= N <=
+ * 2^20 frames.  `work` is device memory of at least p3d_clip_workspace(N) bytes, 8-byte aligned;
+ * every call is a fixed set of launches on `stream` (capturable), never waiting between
+ * workgroups inside a launch: a workgroup owns p3d_clip_chunk() consecutive frames, and what a
+ * hold carries across chunks goes through a second launch.
+ * ------------------------------------------------------------------------------------- */
+int32_t p3d_clip_chunk(void);
+int64_t p3d_clip_workspace(int64_t N);
+
+/* read_openpose_json's smoothing, src/openpose_3dpose_sandbox.py:140-227, then the per-frame input
+ * of :319-351.  smooth != 0 and N >= 9: per coordinate the median of positions i..i+3 (first four
+ * positions), i-3..i (last four) or i-3..i+3, a window of four giving (a + b) / 2 of its middle
+ * values; then the hold in position order: a median equal to 0.0 at position i > 0 takes the
+ * smoothed value of position i - 1 (NaN is not zero).  smooth == 0 or N == 1: xy_s = xy.
+ * 2 <= N <= 8 with smooth != 0: P3D_ERR_ARG (the reference raises, :145-146).
+ *   xy_s [N, 36] float64: the smoothed, held rows (must not alias xy);
+ *   x [N, U2] float32: normalize_data (:348-351) of the joint mapping (:332-342: `order` of :25,
+ *     Hip, Neck/Nose, Thorax) of xy_s over the 64-wide row, rounded to float32 -- the bits of
+ *     p3d_normalize(..., P3D_DTYPE_F32) on the mapped rows, which are never stored.  mean2 / std2
+ *     [64], use2 [U2 <= 64] entries in 0..63 (an entry outside gives NaN). */
+int p3d_clip_prepare(const double* xy, int64_t N, int32_t smooth, const double* mean2, const double* std2,
+                     const int32_t* use2, int32_t U2, float* x, double* xy_s, void* work, int64_t work_bytes,
+                     void* stream);
+
+/* The sandbox's output side, src/openpose_3dpose_sandbox.py:359-417, from the network's rows
+ * y [N, U3] float32 and xy_s: unNormalizeData (:359; (double)v * std + mean as p3d_unnormalize),
+ * per frame over its 32 joints the y / z swap, _max = max(0, max z'), _min = min(10000, min z')
+ * (strict compares, :366-377), z'' = (_max - z') + _min, x += spine_x - 630, z'' += 500 - spine_y
+ * (:379-383; spine = columns 2, 3 of xy_s).  cache_on_fail != 0 (:389-417): a frame whose minimum
+ * over its 96 values is < -1000 (a NaN minimum is not) shows the previous frame's exported pose,
+ * 96 zeros where there is none.  The un-post-processed rows are never stored.
+ *   poses [N, D3 = 96] float64; src [N] int32 (may be NULL): the position each exported pose came
+ *   from, -1 for zeros.  mean3 / std3 [96], use3 [U3 <= 96]. */
+int p3d_clip_finish(const float* y, int64_t N, const double* xy_s, const double* mean3, const double* std3,
+                    const int32_t* use3, int32_t U3, int32_t D3, int32_t cache_on_fail, double* poses,
+                    int32_t* src, void* work, int64_t work_bytes, void* stream);
+
+/* The clip loop of src/openpose_3dpose_sandbox.py:317-417 as one call: p3d_clip_prepare, the eval
+ * forward (keep 1, :353-356) in tiles of max_batch rows through the forward of p3d_lift's
+ * three-step form -- a tile's rows carry p3d_lift's bits at that batch -- and p3d_clip_finish,
+ * all on `stream`.  U2 / U3 must equal the model's input / output size; float32 models.  `work`:
+ * p3d_clip_lift_workspace(N, U2, U3) bytes of device memory, 256-byte aligned (the scan's
+ * summaries and the network's input and output rows).  Capturable. */
+int64_t p3d_clip_lift_workspace(int64_t N, int32_t U2, int32_t U3);
+int p3d_clip_lift(p3d_model* m, const double* xy, int64_t N, int32_t smooth, const double* mean2,
+                  const double* std2, const int32_t* use2, int32_t U2, const double* mean3, const double* std3,
+                  const int32_t* use3, int32_t U3, int32_t D3, int32_t cache_on_fail, double* xy_s, double* poses,
+                  int32_t* src, void* work, int64_t work_bytes, void* stream);
+
 /* np.mean / np.std (population) over axis 0 of x [F, D], D <= 256 -- the statistics of
  * src/data_utils.py:210-211 (normalization_stats).  Deterministic two-level column sums;
  * `work` must hold p3d_moments_workspace(F, D) bytes of device memory. */
