@@ -257,6 +257,9 @@ struct p3d_model {
   int serve6_rt = 0;        // k_serve6 row tiles per unit, 0 = chosen per launch (env P3D_SERVE6_RT: 4 or 2)
   int serve6_depth = 2;     // k_serve6 weight-ring depth of the 7-tile form (env P3D_SERVE6_DEPTH: 2 or 4)
   int serve6_pair = 1;      // XCD-wide units of 10 row tiles as two 5-row-tile units run side by side (env P3D_SERVE6_PAIR: 0 off)
+  // launches of more than serve6_max_nb steps on the pair form with its rounds run back to back
+  // (k_serve6_rounds) where the pair form's conditions hold (env P3D_SERVE6_ROUNDS: 0 off -- k_serve5)
+  int serve6_rounds = 1;
   std::string serve_kname;  // the kernel the last p3d_serve launched (p3d_kernel_name 3)
   // the last k_serve6 launch shape, by batch (serve6_plan prices 64 candidates and the kernel name
   // is a string: both are redone only when the batch changes -- the host enqueue of a serving loop)
@@ -634,6 +637,7 @@ extern "C" int p3d_create(const p3d_cfg* cfg_in, p3d_model** out) {
   if (const char* ev = getenv("P3D_SERVE6_RT")) m->serve6_rt = atoi(ev);
   if (const char* ev = getenv("P3D_SERVE6_DEPTH")) m->serve6_depth = atoi(ev);
   if (const char* ev = getenv("P3D_SERVE6_PAIR")) m->serve6_pair = atoi(ev);
+  if (const char* ev = getenv("P3D_SERVE6_ROUNDS")) m->serve6_rounds = atoi(ev);
   {
     StepState s0{};
     s0.global_step = 0; s0.beta1_power = 0.9f; s0.beta2_power = 0.999f; s0.arrivals = 0;
@@ -1327,10 +1331,11 @@ static Serve6Plan serve6_plan(const p3d_model* m, int64_t B, int T) {
   return best;
 }
 
-static void launch_serve6(const ProfScope& ps, const p3d_model* m, int ncm, int depth, int rt, bool pair,
+static void launch_serve6(const ProfScope& ps, const p3d_model* m, int ncm, int depth, int rt, bool pair, bool rounds,
                           unsigned grid, hipStream_t st, const ServeArgs& a) {
-  if (pair) {   // (serve6 PAIR: two units of rt row tiles per group)
-    go(ps, k_serve6<4, 3, 2, 5, true>, dim3(grid), dim3(256), st, a);
+  if (pair) {   // (serve6 PAIR: two units of rt row tiles per group; long launches: rounds back to back)
+    if (rounds) go(ps, k_serve6_rounds<4, 3, 2, 5>, dim3(grid), dim3(256), st, a);
+    else go(ps, k_serve6<4, 3, 2, 5, true>, dim3(grid), dim3(256), st, a);
     return;
   }
   switch (rt) {   // half-step units (11 column tiles, S = 5) / XCD-wide units (2 tiles, S = 1)
@@ -1452,12 +1457,23 @@ static int serve_impl(p3d_model* m, const float* x, int64_t B, float* y, const f
     }
     s.wsq = c.max_norm ? m->wsq + ly.widx : nullptr;
   }
-  bool use6 = m->serve6 && c.num_layers > 0 && NDT == 3 && (m->serve6 == 2 || a.nb <= (int64_t)m->serve6_max_nb);
+  // A launch of more than serve6_max_nb steps: the pair form with its rounds run back to back
+  // (k_serve6_rounds) where the pair form's conditions hold -- 12 or more k-groups per wave in whole
+  // ring rounds, at most 2 column tiles per member, nothing forcing another shape -- else k_serve5.
+  // (The fused MSE keeps to launches of at most serve6_max_nb steps.)
+  const bool long_launch = a.nb > (int64_t)m->serve6_max_nb;
+  const bool long_pair = long_launch && m->serve6 == 1 && m->serve6_rounds && m->serve6_pair && !t &&
+                         c.num_layers > 0 && NDT == 3 && L / 64 >= 12 && (L / 64) % 4 == 0 &&
+                         m->serve_grid >= 8 && (L / 16 + m->serve_grid / 8 - 1) / (m->serve_grid / 8) <= 2 &&
+                         L / 16 >= m->serve_grid / 8 && (m->serve6_split == 0 || m->serve6_split == 1) &&
+                         (m->serve6_rt == 0 || m->serve6_rt == 10);
+  bool use6 = m->serve6 && c.num_layers > 0 && NDT == 3 && (m->serve6 == 2 || !long_launch || long_pair);
   Serve6Plan plan;
   int depth = 4;
   if (use6) {
     if (B != m->s6_B) {
-      plan = serve6_plan(m, B, L / 16);
+      if (long_pair) { plan.S = 1; plan.rt = 10; plan.ncm = 2; }
+      else plan = serve6_plan(m, B, L / 16);
       // the pair form: an XCD-wide unit of 10 row tiles run as two units of 5 side by side, phases
       // alternating (p3d_serve6.h; the same bits; 20 steps: 99.2 vs 101.1 us, six alternating pairs)
       if (plan.S > 0 && m->serve6_pair && plan.S == 1 && plan.rt == 10 && L / 64 >= 12) {
@@ -1518,10 +1534,15 @@ static int serve_impl(p3d_model* m, const float* x, int64_t B, float* y, const f
   if (use6) {
     a.act = m->serve6_act;                   // [group][4 slabs][16 RT rows][L]; no output partials
     a.part = nullptr;
-    if (m->serve_kname != m->s6_kname) m->serve_kname = m->s6_kname;
+    // (a forced k_serve6 -- P3D_SERVE6=2 -- whose plan is the pair form runs a long launch's rounds
+    // back to back as well)
+    static const std::string rounds_name = "k_serve6_rounds<4, 3, 2, 5>";
+    const bool rounds = plan.pair && long_launch && m->serve6_rounds && !t;
+    const std::string& kname = rounds ? rounds_name : m->s6_kname;
+    if (m->serve_kname != kname) m->serve_kname = kname;
     ProfScope ps(m, "serve");
     HP(2);
-    launch_serve6(ps, m, plan.ncm, depth, plan.rt, plan.pair, (unsigned)m->serve_grid, st, a);
+    launch_serve6(ps, m, plan.ncm, depth, plan.rt, plan.pair, rounds, (unsigned)m->serve_grid, st, a);
     HP(3);
   } else {
     m->serve_kname.clear();

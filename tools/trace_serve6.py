@@ -8,6 +8,9 @@ For every XCD group of the last launch (its first step): rank-0 member and the f
 holding the most column tiles; times in us from the earliest workgroup start (wall_clock64,
 100 MHz).  Columns per hidden phase: contraction, K-combine, epilogue, hand-off wait, then inside the
 epilogue: the K-slice sums (LDS), the epilogue math + stores.
+A launch of more than 32 steps (k_serve6_rounds; P3D_SERVE6_PAIR=1 selects the pair form's columns)
+also prints "round_boundary": the first round's last blocks, the next round's input layers, the
+second round's first blocks and where the first round's output layer runs.
 """
 import ctypes
 import json
@@ -63,6 +66,20 @@ def main():
                         "in_a": us(row[5]), "in_b": us(row[2]), "handoff0": us(row[3]), "first_block": us(row[8]),
                         "last_stores": us(row[8 + 4 * (2 * NH - 1) + 3]), "reduce_end": us(row[8 * (NH + 1)]),
                         "blocks_us": blk})
+            if row[41] > row[0] and row[42] > row[41]:
+                # k_serve6_rounds (a launch of more than 32 steps): the first round boundary.  Stamps of the
+                # second round's blocks 0 / 1 / 2 at 41.. / 49.. / 57.., the next round's input layers done at 45 (unit
+                # A, after block 6) / 46 (unit B, after block 7), the first round's output layer 47 -> 48
+                d = lambda a, b: round((row[a] - row[b]) / 100, 2)   # noqa: E731
+                last = 8 + 4 * (2 * NH - 1)
+                out[-1]["round_boundary"] = {
+                    "ordinary_boundaries_us": [d(8 + 4 * (s + 1), 8 + 4 * s + 1) for s in range(2 * NH - 1)],
+                    "in_a_us": d(45, last - 1), "last_block_contraction_us": d(last + 1, last),
+                    "last_block_epilogue_us": d(last + 3, last + 1), "in_b_us": d(46, last + 3),
+                    "gap_last_to_first_contraction_us": d(41, last + 1),
+                    "block0_us": [d(42, 41), d(43, 42), d(44, 43)], "block0_to_block1_us": d(49, 42),
+                    "block1_contraction_us": d(50, 49), "out_phase_us": d(48, 47), "out_phase_after_block1_us": d(47, 50),
+                    "block1_to_block2_us": d(57, 50), "block2_contraction_us": d(58, 57)}
             continue
         ph = []
         for p in range(1, NH + 1):
