@@ -66,6 +66,7 @@ SIGNATURES = [
     ("p3d_mpjpe_accum_ex", c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int64,
                                      c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     ("p3d_kernel_name", c_int32, [c_void_p, c_int32, c_char_p, c_int64]),
+    ("p3d_serve_plan", c_int32, [POINTER(P3DCfg), c_int32, c_int64, c_int32, c_char_p, c_int64, POINTER(c_int32)]),
     ("p3d_dlpack_alias", c_void_p, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32]),
     ("p3d_train_step", c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_float, c_uint64, c_float,
                                  c_float, c_float, c_void_p, c_void_p]),

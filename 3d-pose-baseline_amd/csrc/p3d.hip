@@ -22,6 +22,7 @@
 #include "p3d_clip.h"
 #include "p3d_serve.h"
 #include "p3d_serve6.h"
+#include "p3d_serve_plan.h"
 #include "p3d_gemv.h"
 #include "p3d_xchg.h"
 #include "../../include/p3d.h"
@@ -251,21 +252,12 @@ struct p3d_model {
   // 109.5 vs 102.2 us per cfg3 step; each layer's on a side stream, 197-202 vs 122 us -- DESIGN 5c)
   float* alpha_dev = nullptr;    // the step's Adam alpha, formed by the first backward launch
   bool step_advanced = false;    // set by a backward whose last launch advanced the step state
-  int serve6 = 1;           // k_serve6 for launches of <= serve6_max_nb steps (env P3D_SERVE6: 0 off, 1 auto, 2 always)
-  int serve6_max_nb = 32;   // (env P3D_SERVE6_MAX_NB)
-  int serve6_split = 0;     // k_serve6 groups per XCD, 0 = chosen per launch (env P3D_SERVE6_SPLIT: 1..8)
-  int serve6_rt = 0;        // k_serve6 row tiles per unit, 0 = chosen per launch (env P3D_SERVE6_RT: 4 or 2)
-  int serve6_depth = 2;     // k_serve6 weight-ring depth of the 7-tile form (env P3D_SERVE6_DEPTH: 2 or 4)
-  int serve6_pair = 1;      // XCD-wide units of 10 row tiles as two 5-row-tile units run side by side (env P3D_SERVE6_PAIR: 0 off)
-  // launches of more than serve6_max_nb steps on the pair form with its rounds run back to back
-  // (k_serve6_rounds) where the pair form's conditions hold (env P3D_SERVE6_ROUNDS: 0 off -- k_serve5)
-  int serve6_rounds = 1;
-  std::string serve_kname;  // the kernel the last p3d_serve launched (p3d_kernel_name 3)
-  // the last k_serve6 launch shape, by batch (serve6_plan prices 64 candidates and the kernel name
-  // is a string: both are redone only when the batch changes -- the host enqueue of a serving loop)
-  int64_t s6_B = -1;
-  struct { int S, rt, ncm; bool pair; int depth; } s6_shape{};
-  std::string s6_kname;
+  ServeKnobs serve_knobs;   // env P3D_SERVE6* (p3d_serve_plan.h)
+  // the last launch's choice, by (batch, with loss): serve_plan prices 64 candidates, redone only
+  // when the key changes -- the host enqueue of a serving loop
+  int64_t serve_B = -1;
+  bool serve_with_loss = false;
+  ServeChoice serve_choice;
   // data-parallel step with the library's own all-reduce (p3d_dp.h)
   p3d_comm* comm = nullptr;      // not owned (p3d_comm_create / p3d_comm_destroy)
   hipStream_t cst = nullptr;     // comm stream (non-blocking), forked from / joined to the caller's stream
@@ -631,13 +623,7 @@ extern "C" int p3d_create(const p3d_cfg* cfg_in, p3d_model** out) {
   if ((e = hipMalloc(&m->hcnt, 512 * sizeof(unsigned))) != hipSuccess) return cleanup(e);
   if ((e = hipMemset(m->hcnt, 0, 512 * sizeof(unsigned))) != hipSuccess) return cleanup(e);
   if (const char* ev = getenv("P3D_SERVE_GROUPS")) m->serve_groups = atoi(ev);
-  if (const char* ev = getenv("P3D_SERVE6")) m->serve6 = atoi(ev);
-  if (const char* ev = getenv("P3D_SERVE6_MAX_NB")) m->serve6_max_nb = atoi(ev);
-  if (const char* ev = getenv("P3D_SERVE6_SPLIT")) m->serve6_split = atoi(ev);
-  if (const char* ev = getenv("P3D_SERVE6_RT")) m->serve6_rt = atoi(ev);
-  if (const char* ev = getenv("P3D_SERVE6_DEPTH")) m->serve6_depth = atoi(ev);
-  if (const char* ev = getenv("P3D_SERVE6_PAIR")) m->serve6_pair = atoi(ev);
-  if (const char* ev = getenv("P3D_SERVE6_ROUNDS")) m->serve6_rounds = atoi(ev);
+  m->serve_knobs = serve_knobs_from_env();
   {
     StepState s0{};
     s0.global_step = 0; s0.beta1_power = 0.9f; s0.beta2_power = 0.999f; s0.arrivals = 0;
@@ -1254,117 +1240,62 @@ extern "C" int p3d_forward(p3d_model* m, const float* x, int64_t B, float* y, in
   return p3d_forward_ex(m, x, B, y, training, keep_prob, seed, ctr, row_offset, 0, stream);
 }
 
-// ---- persistent XCD-local evaluation (k_serve, p3d_serve.h) ---------------------------
-// k_serve (models without residual blocks): 4 K slices per unit, a 2-deep register ring.
-// k_serve5: a 4-deep ring where each wave's L / 64 k-groups allow it, else 2 (p3d_serve needs
-// L % 128 == 0, so L / 64 is even); depth 8 spilled 186 registers and measured 8.1 M poses/s vs
-// 12.9 M at depth 4, so it is not built.
-static int serve5_depth(int L) { return (L / 64) % 4 == 0 ? 4 : 2; }
+// ---- persistent XCD-local evaluation (p3d_serve.h, p3d_serve6.h) ------------------------
+// Which kernel a launch runs is decided in p3d_serve_plan.h (the list of built forms and the
+// planner over it); here the kernels are attached to that list, row for row.
+static_assert(kServe6Rows == P3D_SERVE6_ROWS, "p3d_serve_plan.h plans for the slabs p3d_serve.h sizes");
+#define SERVE_KERNEL_k_serve(D, NDT, NCM, RT, PAIR) k_serve<D, NDT, 4>
+#define SERVE_KERNEL_k_serve5(D, NDT, NCM, RT, PAIR) k_serve5<D, NDT, 2, 2>
+#define SERVE_KERNEL_k_serve6(D, NDT, NCM, RT, PAIR) k_serve6<D, NDT, NCM, RT, PAIR>
+#define SERVE_KERNEL_k_serve6_rounds(D, NDT, NCM, RT, PAIR) k_serve6_rounds<D, NDT, NCM, RT>
+#define SERVE_KERNEL_ROW(KIND, D, NDT, NCM, RT, PAIR) SERVE_KERNEL_##KIND(D, NDT, NCM, RT, PAIR),
+static void (*const kServeKernels[])(ServeArgs) = {P3D_SERVE_FORMS(SERVE_KERNEL_ROW)};
+#undef SERVE_KERNEL_ROW
 
-template <int NDT>
-static void launch_serve_k(const ProfScope& ps, unsigned grid, hipStream_t st, const ServeArgs& a) {
-  if (a.nblk > 0) {   // k_serve5: 4-wave workgroups, two groups per XCD, paired units, steps pipelined
-    if (serve5_depth(a.L) == 4) go(ps, k_serve5<4, NDT, 2, 2>, dim3(grid), dim3(256), st, a);
-    else go(ps, k_serve5<2, NDT, 2, 2>, dim3(grid), dim3(256), st, a);
-    return;
-  }
-  go(ps, k_serve<2, NDT, 4>, dim3(grid), dim3(512), st, a);
+#define SERVE_TRY(expr)                                                                                     \
+  do {                                                                                                      \
+    hipError_t e_ = (expr);                                                                                 \
+    if (e_ != hipSuccess) return fail(P3D_ERR_HIP, std::string("p3d_serve: ") + hipGetErrorString(e_)); \
+  } while (0)
+
+// Why p3d_serve does not take this model shape or batch (nullptr: it does).
+static const char* serve_shape_error(const p3d_cfg& c, int64_t B) {
+  if (B <= 0) return "p3d_serve: batch must be positive";
+  if (c.dtype != P3D_DTYPE_F32) return "p3d_serve: fp32 models only";
+  if (c.linear_size <= 0 || c.linear_size % 128 != 0 || c.input_size > 64 || c.output_size > 64 ||
+      2 * c.num_layers + 2 > P3D_SERVE_MAXL)
+    return "p3d_serve: needs linear_size % 128 == 0, input/output size <= 64, <= 7 blocks";
+  if ((B + 63) / 64 > 0x7fffffff) return "p3d_serve: too many rows";
+  return nullptr;
 }
 
-// ---- k_serve6 (p3d_serve6.h): launches of a few dozen steps ----------------------------
-// Groups per XCD for nb steps: the S minimising (rounds of steps) x (fixed cost per phase +
-// cost per column tile x tiles per CU), with 32 CUs per XCD (grid / 8): a phase's fixed cost
-// (hand-off, ring fill, K-combine, epilogue) ~4 us, a column tile of K = 1024 ~3.9 us
-// (round-1 phase traces).  nb = 20 -> S = 3 (all steps at once, <= 7 tiles per
-// CU); nb <= 8 -> S = 1; nb = 16 -> S = 2.
-// A k_serve6 launch shape: S groups per XCD, RT row tiles per unit (4: batch-64 steps, 2:
-// 32-row half steps), NCM column tiles per contraction (the built form covering a member of the
-// smallest group; its epilogue constants of at most ECT tiles sit in LDS, p3d_serve6.h).
-struct Serve6Plan { int S = 0, rt = 4, ncm = 0; bool pair = false; };
-
-// the built (RT, NCM) forms: batch-64 units with 2 / 4 / 7 / 8 column tiles per CU, half-step
-// units with 11 (S = 5) or 2 (S = 1), 16-row units with 2 (S = 1: a lone batch-64 request on
-// four XCDs), and XCD-wide units (S = 1, 2 tiles per CU) of 6 .. 16 row tiles
-static int serve6_ncm_for(int rt, int need) {
-  if (rt == 1) return need <= 2 ? 2 : 0;
-  if (rt == 2) return need <= 2 ? 2 : need <= 11 ? 11 : 0;
-  if (rt == 4) return need <= 2 ? 2 : need <= 4 ? 4 : need <= 7 ? 7 : need <= 8 ? 8 : 0;
-  return need <= 2 ? 2 : 0;
-}
-
-// The plan minimising (rounds of units) x (fixed cost per phase + cost per column tile x tiles
-// per CU), 32 CUs per XCD (grid / 8): a phase's fixed cost (hand-off, ring fill, K-combine,
-// epilogue) ~4 us, a column tile of K = 1024 ~3.9 us at 4 row tiles, proportional to the row
-// tiles (round-1 phase traces).  20 batch-64 steps (1280 rows): RT = 10, S = 1 --
-// 160 rows per XCD, 2 column tiles per CU (the half-step form, RT = 2 with 5 groups per XCD,
-// costs 11 tiles of 2 row tiles per CU: 22 vs 20 tile-units and 5x the weight reads).  A
-// wide form (NCM >= 7) is priced at its full width: its register ring and epilogue run NCM
-// tiles whatever share of them a member owns.  One batch-64 request: RT = 1, four 16-row units
-// on four XCDs, 2 tiles per CU (vs one XCD at RT = 4).
-static Serve6Plan serve6_plan(const p3d_model* m, int64_t B, int T) {
-  static const int rts[] = {4, 2, 1, 6, 8, 10, 12, 16};
-  const int cx = std::max(1, m->serve_grid / 8);
-  const double cfix = 4.0;
-  Serve6Plan best;
-  double bt = 1e30;
-  for (int rt : rts) {
-    if (m->serve6_rt && m->serve6_rt != rt) continue;
-    if ((rt > 4 || rt == 1) && (T / 4) % 4 != 0) continue;   // these forms run a 4-deep weight ring
-    const int64_t nb = (B + 16 * rt - 1) / (16 * rt);
-    const double ctile = 3.9 * (rt / 4.0) * T / 64.0;
-    for (int S = 1; S <= 8; ++S) {
-      if (m->serve6_split && m->serve6_split != S) continue;
-      const int nmin = cx / S;
-      if (nmin < 1) continue;
-      // the plan's activation slabs must fit serve6_act (8 S groups of 16 RT rows, P3D_SERVE6_ROWS):
-      // only plans that fit are priced (a cap applied after the choice dropped a launch
-      // whose best plan did not fit to k_serve5 instead of the best plan that did)
-      if ((int64_t)8 * S * 16 * rt > P3D_SERVE6_ROWS) continue;
-      const int need = (T + nmin - 1) / nmin, ncm = serve6_ncm_for(rt, need);
-      if (!ncm || need > (ncm >= 7 ? ncm : 2 * ncm)) continue;
-      const double rounds = (double)((nb + 8 * S - 1) / (8 * S));
-      if (rt == 2 && ncm == 2 && (T / 4) % 4 != 0) continue;
-      const double t = rounds * (cfix + ctile * (ncm >= 7 ? ncm : need));
-      if (t < bt - 1e-9) { bt = t; best.S = S; best.rt = rt; best.ncm = ncm; }
-    }
-  }
-  return best;
-}
-
-static void launch_serve6(const ProfScope& ps, const p3d_model* m, int ncm, int depth, int rt, bool pair, bool rounds,
-                          unsigned grid, hipStream_t st, const ServeArgs& a) {
-  if (pair) {   // (serve6 PAIR: two units of rt row tiles per group; long launches: rounds back to back)
-    if (rounds) go(ps, k_serve6_rounds<4, 3, 2, 5>, dim3(grid), dim3(256), st, a);
-    else go(ps, k_serve6<4, 3, 2, 5, true>, dim3(grid), dim3(256), st, a);
-    return;
-  }
-  switch (rt) {   // half-step units (11 column tiles, S = 5) / XCD-wide units (2 tiles, S = 1)
-    case 1: go(ps, k_serve6<4, 3, 2, 1>, dim3(grid), dim3(256), st, a); return;
-    case 2:
-      if (ncm == 2) go(ps, k_serve6<4, 3, 2, 2>, dim3(grid), dim3(256), st, a);
-      else go(ps, k_serve6<2, 3, 11, 2>, dim3(grid), dim3(256), st, a);
-      return;
-    case 6: go(ps, k_serve6<4, 3, 2, 6>, dim3(grid), dim3(256), st, a); return;
-    case 8: go(ps, k_serve6<4, 3, 2, 8>, dim3(grid), dim3(256), st, a); return;
-    case 10: go(ps, k_serve6<4, 3, 2, 10>, dim3(grid), dim3(256), st, a); return;
-    case 12: go(ps, k_serve6<4, 3, 2, 12>, dim3(grid), dim3(256), st, a); return;
-    case 16: go(ps, k_serve6<4, 3, 2, 16>, dim3(grid), dim3(256), st, a); return;
-    default: break;
-  }
-  // ring depth 4 for the narrow forms; 2 for 7 / 8 tiles (depth 4 spills there: 77 / 136
-  // registers; depth 2 none / 38)
-  if (ncm == 2) {
-    if (depth == 4) go(ps, k_serve6<4, 3, 2>, dim3(grid), dim3(256), st, a);
-    else go(ps, k_serve6<2, 3, 2>, dim3(grid), dim3(256), st, a);
-  } else if (ncm == 4) {
-    if (depth == 4) go(ps, k_serve6<4, 3, 4>, dim3(grid), dim3(256), st, a);
-    else go(ps, k_serve6<2, 3, 4>, dim3(grid), dim3(256), st, a);
-  } else if (ncm == 7) {
-    if (depth == 4) go(ps, k_serve6<4, 3, 7>, dim3(grid), dim3(256), st, a);   // weights 4 ahead (53 spills)
-    else go(ps, k_serve6<2, 3, 7>, dim3(grid), dim3(256), st, a);
-  } else {
-    go(ps, k_serve6<2, 3, 8>, dim3(grid), dim3(256), st, a);
-  }
+// The first call's buffers, k_serve6's with the others: a later call that takes
+// k_serve6 for the first time may be inside a graph capture, where hipMalloc is not allowed.
+static int serve_alloc(p3d_model* m) {
+  const p3d_cfg& c = m->cfg;
+  const int L = c.linear_size, U = L / 32, NDT = (c.output_size + 15) / 16;
+  const int64_t slab = (int64_t)64 * L, PT = (int64_t)4 * NDT * 256;
+  int dev = 0, cus = 0;
+  SERVE_TRY(hipGetDevice(&dev));
+  SERVE_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  m->serve_grid = cus;   // one 512-thread workgroup per CU (the LDS ring admits one)
+  // output partials: k_serve5 keeps one per 32-column unit (U), k_serve6 one per 16-column tile (2U)
+  const int64_t nbuf = P3D_SERVE_GROUPS * 3 * slab + P3D_SERVE_GROUPS * 2 * (int64_t)(2 * U) * PT;
+  SERVE_TRY(hipMalloc(&m->serve_buf, nbuf * sizeof(float)));
+  SERVE_TRY(hipMemset(m->serve_buf, 0, nbuf * sizeof(float)));
+  // [bank 0 | bank 1 | k_serve5 bank | epoch word]: k_serve6 alternates banks 0 / 1 by the
+  // device epoch word (p3d_serve6.h), k_serve5 uses bank 2 (zeroed before each of its launches)
+  SERVE_TRY(hipMalloc(&m->serve_sync, P3D_SERVE_SYNC_ALL * sizeof(unsigned)));
+  SERVE_TRY(hipMemset(m->serve_sync, 0, P3D_SERVE_SYNC_ALL * sizeof(unsigned)));
+  const int64_t necg = (int64_t)(2 * c.num_layers + 2) * (L / 16) * 48 + 64;
+  SERVE_TRY(hipMalloc(&m->serve_ecg, necg * sizeof(float)));
+  SERVE_TRY(hipMalloc(&m->serve6_act, (int64_t)4 * P3D_SERVE6_ROWS * L * sizeof(float)));
+  // the fused MSE's per-tile partials (kServeLossTiles: serve_plan refuses a loss over more) and
+  // its arrival counter (the word after them), zero between launches
+  SERVE_TRY(hipMalloc(&m->serve_loss, (kServeLossTiles + 64) * sizeof(float)));
+  SERVE_TRY(hipMemset(m->serve_loss, 0, (kServeLossTiles + 64) * sizeof(float)));
+  m->serve_ec_dirty = true;
+  return P3D_OK;
 }
 
 static int serve_impl(p3d_model* m, const float* x, int64_t B, float* y, const float* t, float* loss,
@@ -1372,13 +1303,8 @@ static int serve_impl(p3d_model* m, const float* x, int64_t B, float* y, const f
   HP_START
   if (!m || !x || !y) return fail(P3D_ERR_ARG, "p3d_serve: null argument");
   const p3d_cfg& c = m->cfg;
-  if (B <= 0) return fail(P3D_ERR_ARG, "p3d_serve: batch must be positive");
-  if (c.dtype != P3D_DTYPE_F32) return fail(P3D_ERR_ARG, "p3d_serve: fp32 models only");
-  if (c.linear_size % 128 != 0 || c.input_size > 64 || c.output_size > 64 ||
-      2 * c.num_layers + 2 > P3D_SERVE_MAXL)
-    return fail(P3D_ERR_ARG, "p3d_serve: needs linear_size % 128 == 0, input/output size <= 64, <= 7 blocks");
+  if (const char* why = serve_shape_error(c, B)) return fail(P3D_ERR_ARG, why);
   if (!aligned16(x)) return fail(P3D_ERR_ARG, "p3d_serve: x must be 16-byte aligned");
-  if ((B + 63) / 64 > 0x7fffffff) return fail(P3D_ERR_ARG, "p3d_serve: too many rows");
   // an earlier launch failed and nobody has collected the error (p3d_serve_check): refuse, so a
   // caller never keeps receiving rows of a launch whose workgroups could not synchronise
   if (m->errw && m->errw[1])
@@ -1398,49 +1324,16 @@ static int serve_impl(p3d_model* m, const float* x, int64_t B, float* y, const f
     if (r == P3D_OK && m->hwait) m->harmed = true;
     if (r != 1) return r;   // (1: no chain form for this model -- k_serve6 below)
   }
-  const int L = c.linear_size, U = L / 32, NDT = (c.output_size + 15) / 16;
-  const int64_t slab = (int64_t)64 * L, PT = (int64_t)4 * NDT * 256;
-  hipError_t e;
   if (!m->serve_buf) {
-    int dev = 0, cus = 0;
-    if ((e = hipGetDevice(&dev)) != hipSuccess) return fail(P3D_ERR_HIP, std::string("p3d_serve: ") + hipGetErrorString(e));
-    if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess)
-      return fail(P3D_ERR_HIP, std::string("p3d_serve: ") + hipGetErrorString(e));
-    m->serve_grid = cus;   // one 512-thread workgroup per CU (the LDS ring admits one)
-    // output partials: k_serve5 keeps one per 32-column unit (U), k_serve6 one per 16-column tile (2U)
-    const int64_t nbuf = P3D_SERVE_GROUPS * 3 * slab + P3D_SERVE_GROUPS * 2 * (int64_t)(2 * U) * PT;
-    if ((e = hipMalloc(&m->serve_buf, nbuf * sizeof(float))) != hipSuccess)
-      return fail(P3D_ERR_HIP, std::string("p3d_serve: ") + hipGetErrorString(e));
-    if ((e = hipMemset(m->serve_buf, 0, nbuf * sizeof(float))) != hipSuccess)
-      return fail(P3D_ERR_HIP, std::string("p3d_serve: ") + hipGetErrorString(e));
-    // [bank 0 | bank 1 | k_serve5 bank | epoch word]: k_serve6 alternates banks 0 / 1 by the
-    // device epoch word (p3d_serve6.h), k_serve5 uses bank 2 (zeroed before each of its launches)
-    if ((e = hipMalloc(&m->serve_sync, P3D_SERVE_SYNC_ALL * sizeof(unsigned))) != hipSuccess)
-      return fail(P3D_ERR_HIP, std::string("p3d_serve: ") + hipGetErrorString(e));
-    if ((e = hipMemset(m->serve_sync, 0, P3D_SERVE_SYNC_ALL * sizeof(unsigned))) != hipSuccess)
-      return fail(P3D_ERR_HIP, std::string("p3d_serve: ") + hipGetErrorString(e));
-    const int64_t necg = (int64_t)(2 * c.num_layers + 2) * (L / 16) * 48 + 64;
-    if ((e = hipMalloc(&m->serve_ecg, necg * sizeof(float))) != hipSuccess)
-      return fail(P3D_ERR_HIP, std::string("p3d_serve: ") + hipGetErrorString(e));
-    // k_serve6's activation slabs, here with the other first-call buffers: a later
-    // call that takes k_serve6 for the first time may be inside a graph capture, where hipMalloc
-    // is not allowed
-    const int64_t n6 = (int64_t)4 * P3D_SERVE6_ROWS * L;
-    if ((e = hipMalloc(&m->serve6_act, n6 * sizeof(float))) != hipSuccess)
-      return fail(P3D_ERR_HIP, std::string("p3d_serve: ") + hipGetErrorString(e));
-    // the fused MSE's per-tile partials (one per 16-row x 16-column output tile of P3D_SERVE6_ROWS
-    // rows) and its arrival counter (last word), zero between launches
-    if ((e = hipMalloc(&m->serve_loss, (P3D_SERVE6_ROWS / 16 * 4 + 64) * sizeof(float))) != hipSuccess)
-      return fail(P3D_ERR_HIP, std::string("p3d_serve: ") + hipGetErrorString(e));
-    if ((e = hipMemset(m->serve_loss, 0, (P3D_SERVE6_ROWS / 16 * 4 + 64) * sizeof(float))) != hipSuccess)
-      return fail(P3D_ERR_HIP, std::string("p3d_serve: ") + hipGetErrorString(e));
-    m->serve_ec_dirty = true;
+    const int r = serve_alloc(m);
+    if (r != P3D_OK) return r;
   }
+  const int L = c.linear_size;
   ServeArgs a{};
-  a.x = x; a.y = y; a.M = B; a.nb = (int)((B + 63) / 64);   // batch-64 steps (k_serve6 may halve them)
+  a.x = x; a.y = y; a.M = B;
   a.L = L; a.K0 = c.input_size; a.ND = c.output_size; a.nblk = c.num_layers;
   a.bn = c.batch_norm; a.residual = c.residual; a.eps = c.bn_eps;
-  a.act = m->serve_buf; a.part = m->serve_buf + P3D_SERVE_GROUPS * 3 * slab;
+  a.act = m->serve_buf; a.part = m->serve_buf + P3D_SERVE_GROUPS * 3 * (int64_t)64 * L;
   a.sync = m->serve_sync; a.err = m->serve_err;
   a.epoch = m->serve_sync + 3 * P3D_SERVE_SYNC_WORDS;
   a.census_extra = m->serve_fault ? 1 : 0;
@@ -1457,54 +1350,23 @@ static int serve_impl(p3d_model* m, const float* x, int64_t B, float* y, const f
     }
     s.wsq = c.max_norm ? m->wsq + ly.widx : nullptr;
   }
-  // A launch of more than serve6_max_nb steps: the pair form with its rounds run back to back
-  // (k_serve6_rounds) where the pair form's conditions hold -- 12 or more k-groups per wave in whole
-  // ring rounds, at most 2 column tiles per member, nothing forcing another shape -- else k_serve5.
-  // (The fused MSE keeps to launches of at most serve6_max_nb steps.)
-  const bool long_launch = a.nb > (int64_t)m->serve6_max_nb;
-  const bool long_pair = long_launch && m->serve6 == 1 && m->serve6_rounds && m->serve6_pair && !t &&
-                         c.num_layers > 0 && NDT == 3 && L / 64 >= 12 && (L / 64) % 4 == 0 &&
-                         m->serve_grid >= 8 && (L / 16 + m->serve_grid / 8 - 1) / (m->serve_grid / 8) <= 2 &&
-                         L / 16 >= m->serve_grid / 8 && (m->serve6_split == 0 || m->serve6_split == 1) &&
-                         (m->serve6_rt == 0 || m->serve6_rt == 10);
-  bool use6 = m->serve6 && c.num_layers > 0 && NDT == 3 && (m->serve6 == 2 || !long_launch || long_pair);
-  Serve6Plan plan;
-  int depth = 4;
-  if (use6) {
-    if (B != m->s6_B) {
-      if (long_pair) { plan.S = 1; plan.rt = 10; plan.ncm = 2; }
-      else plan = serve6_plan(m, B, L / 16);
-      // the pair form: an XCD-wide unit of 10 row tiles run as two units of 5 side by side, phases
-      // alternating (p3d_serve6.h; the same bits; 20 steps: 99.2 vs 101.1 us, six alternating pairs)
-      if (plan.S > 0 && m->serve6_pair && plan.S == 1 && plan.rt == 10 && L / 64 >= 12) {
-        plan.rt = 5;
-        plan.pair = true;
-      }
-      const int T = L / 16, ncm = plan.ncm;
-      depth = ((ncm <= 4 || (ncm == 7 && m->serve6_depth == 4)) && (T / 4) % 4 == 0) ? 4 : 2;
-      if (plan.rt == 2) depth = ncm == 2 ? 4 : 2;
-      if (plan.rt == 1) depth = 4;
-      if (plan.rt > 4) depth = 4;   // (an 8-deep weight ring measured 117 vs 107-112 us at RT = 10)
-      m->s6_shape = {plan.S, plan.rt, plan.ncm, plan.pair, depth};
-      m->s6_kname = plan.S > 0 ? "k_serve6<" + std::to_string(depth) + ", 3, " + std::to_string(ncm) + ", " +
-                                     std::to_string(plan.rt) + (plan.pair ? ", true>" : ">")
-                               : std::string();
-      m->s6_B = B;
-    }
-    plan.S = m->s6_shape.S; plan.rt = m->s6_shape.rt; plan.ncm = m->s6_shape.ncm; plan.pair = m->s6_shape.pair;
-    depth = m->s6_shape.depth;
-    a.split = plan.S;
-    use6 = plan.S > 0;                       // no form covers this width: k_serve5
-    if (use6) a.nb = (int)((B + 16 * plan.rt - 1) / (16 * plan.rt));   // units of 16 RT rows
+  if (B != m->serve_B || (t != nullptr) != m->serve_with_loss) {
+    const ServeChoice ch = serve_plan(L, c.num_layers, (c.output_size + 15) / 16, m->serve_grid, m->serve_knobs, B,
+                                      t != nullptr);
+    if (ch.refused) return fail(P3D_ERR_ARG, ch.refused);
+    m->serve_choice = ch; m->serve_B = B; m->serve_with_loss = t != nullptr;
   }
+  const ServeForm& f = *m->serve_choice.form;
+  const bool use6 = f.kind == SK_k_serve6 || f.kind == SK_k_serve6_rounds;
+  a.split = m->serve_choice.S;
+  a.nb = m->serve_choice.nb;   // batch-64 steps, or k_serve6's units of 16 RT rows
   a.ecg = m->serve_ecg;
   // a HIP graph being captured replays this call with whatever parameters it then finds: the
   // epilogue-constant table is formed inside the graph (one small launch per replay), not
   // decided once at capture time
   HP(0);
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if ((e = hipStreamIsCapturing(st, &cap)) != hipSuccess)
-    return fail(P3D_ERR_HIP, std::string("p3d_serve: ") + hipGetErrorString(e));
+  SERVE_TRY(hipStreamIsCapturing(st, &cap));
   const bool capturing = cap != hipStreamCaptureStatusNone;
   HP(1);
 
@@ -1516,46 +1378,28 @@ static int serve_impl(p3d_model* m, const float* x, int64_t B, float* y, const f
     LAUNCH_CHECK("k_serve_prep");
     if (!capturing) m->serve_ec_dirty = false;
   }
-  if (!use6) {   // k_serve5: its own bank, zeroed in front of every launch
-    a.sync = m->serve_sync + 2 * P3D_SERVE_SYNC_WORDS;
-    if ((e = hipMemsetAsync(a.sync, 0, P3D_SERVE_SYNC_WORDS * sizeof(unsigned), st)) != hipSuccess)
-      return fail(P3D_ERR_HIP, std::string("p3d_serve: ") + hipGetErrorString(e));
-  }
-  // (k_serve6 picks its bank from the device epoch word: no memset in front, graph replays
-  // alternate the banks by themselves)
-  if (t && !use6)
-    return fail(P3D_ERR_ARG, "p3d_serve_mse: no k_serve6 form covers this launch (more than 32 batch-64 steps, "
-                             "or a model shape k_serve6 is not built for): use p3d_serve + p3d_mse");
-  if (t) {
-    a.tgt = t; a.loss = loss;
-    a.lpart = m->serve_loss; a.lcnt = (unsigned*)(m->serve_loss + P3D_SERVE6_ROWS / 16 * 4);
-    if (m->hwait && use6 && !plan.pair) { a.hflag = m->hflag_dev; a.hseq = m->hwait; m->harmed = true; }
-  }
   if (use6) {
+    // (k_serve6 picks its bank from the device epoch word: no memset in front, graph replays
+    // alternate the banks by themselves)
     a.act = m->serve6_act;                   // [group][4 slabs][16 RT rows][L]; no output partials
     a.part = nullptr;
-    // (a forced k_serve6 -- P3D_SERVE6=2 -- whose plan is the pair form runs a long launch's rounds
-    // back to back as well)
-    static const std::string rounds_name = "k_serve6_rounds<4, 3, 2, 5>";
-    const bool rounds = plan.pair && long_launch && m->serve6_rounds && !t;
-    const std::string& kname = rounds ? rounds_name : m->s6_kname;
-    if (m->serve_kname != kname) m->serve_kname = kname;
-    ProfScope ps(m, "serve");
-    HP(2);
-    launch_serve6(ps, m, plan.ncm, depth, plan.rt, plan.pair, rounds, (unsigned)m->serve_grid, st, a);
-    HP(3);
-  } else {
-    m->serve_kname.clear();
-    ProfScope ps(m, "serve");
-    const unsigned grid = (unsigned)m->serve_grid;
-    if (NDT == 1) launch_serve_k<1>(ps, grid, st, a);
-    else if (NDT == 2) launch_serve_k<2>(ps, grid, st, a);
-    else if (NDT == 3) launch_serve_k<3>(ps, grid, st, a);
-    else launch_serve_k<4>(ps, grid, st, a);
+  } else {   // k_serve5: its own bank, zeroed in front of every launch
+    a.sync = m->serve_sync + 2 * P3D_SERVE_SYNC_WORDS;
+    SERVE_TRY(hipMemsetAsync(a.sync, 0, P3D_SERVE_SYNC_WORDS * sizeof(unsigned), st));
   }
+  if (t) {   // (serve_plan lets only k_serve6 forms carry the loss)
+    a.tgt = t; a.loss = loss;
+    a.lpart = m->serve_loss; a.lcnt = (unsigned*)(m->serve_loss + kServeLossTiles);
+    if (m->hwait && !f.pair) { a.hflag = m->hflag_dev; a.hseq = m->hwait; m->harmed = true; }
+  }
+  ProfScope ps(m, "serve");
+  HP(2);
+  go(ps, kServeKernels[&f - kServeForms], dim3((unsigned)m->serve_grid), dim3(f.kind == SK_k_serve ? 512 : 256), st, a);
+  HP(3);
   LAUNCH_CHECK("k_serve");
   return P3D_OK;
 }
+#undef SERVE_TRY
 
 extern "C" int p3d_serve(p3d_model* m, const float* x, int64_t B, float* y, void* stream) {
   return serve_impl(m, x, B, y, nullptr, nullptr, stream);
@@ -1566,6 +1410,22 @@ extern "C" int p3d_serve_mse(p3d_model* m, const float* x, int64_t B, float* y, 
                              void* stream) {
   if (!t || !loss) return fail(P3D_ERR_ARG, "p3d_serve_mse: null argument");
   return serve_impl(m, x, B, y, t, loss, stream);
+}
+
+// (include/p3d.h) the planner's answer for a model shape and device size, no GPU touched
+extern "C" int p3d_serve_plan(const p3d_cfg* cfg, int32_t cus, int64_t B, int32_t with_loss, char* name,
+                              int64_t name_len, int32_t* shape) {
+  if (!cfg || !name || name_len <= 0 || cus < 1) return fail(P3D_ERR_ARG, "p3d_serve_plan: bad argument");
+  if (const char* why = serve_shape_error(*cfg, B)) return fail(P3D_ERR_ARG, why);
+  const ServeChoice ch = serve_plan(cfg->linear_size, cfg->num_layers, (cfg->output_size + 15) / 16, cus,
+                                    serve_knobs_from_env(), B, with_loss != 0);
+  if (ch.refused) return fail(P3D_ERR_ARG, ch.refused);
+  strncpy(name, serve_form_name(*ch.form).c_str(), (size_t)name_len - 1);
+  name[name_len - 1] = 0;
+  if (shape) {
+    shape[0] = ch.S; shape[1] = ch.form->rt; shape[2] = ch.form->ncm; shape[3] = ch.form->depth; shape[4] = ch.nb;
+  }
+  return P3D_OK;
 }
 
 static const char* serve_err_text(int v) {
@@ -1579,7 +1439,7 @@ static int serve_report(p3d_model* m, int v) {
   hipError_t e = hipDeviceSynchronize();
   if (e == hipSuccess && m->serve_sync) e = hipMemset(m->serve_sync, 0, P3D_SERVE_SYNC_ALL * sizeof(unsigned));
   // (a failed launch may have left the fused MSE's arrival counter short)
-  if (e == hipSuccess && m->serve_loss) e = hipMemset(m->serve_loss, 0, (P3D_SERVE6_ROWS / 16 * 4 + 64) * sizeof(float));
+  if (e == hipSuccess && m->serve_loss) e = hipMemset(m->serve_loss, 0, (kServeLossTiles + 64) * sizeof(float));
   if (e != hipSuccess) return fail(P3D_ERR_HIP, std::string("p3d_serve_check: ") + hipGetErrorString(e));
   __atomic_store_n(&m->errw[1], 0, __ATOMIC_SEQ_CST);
   return fail(P3D_ERR_HIP, serve_err_text(v));
@@ -2208,14 +2068,12 @@ extern "C" int p3d_kernel_name(const p3d_model* m, int32_t what, char* out, int6
     // the optimizers' weight source (bench.py's byte count): "packed" = W read from its Wd copy, the
     // TF-layout master not written (28 B per weight element per fused step); "master" = 32 B
     n = m->w_pk ? "packed" : "master";
-  } else if (what == 3 && !m->serve_kname.empty()) {
-    n = m->serve_kname;     // the kernel the last p3d_serve launched
-  } else if (what == 3) {
-    const int ndt = (m->cfg.output_size + 15) / 16, L = m->cfg.linear_size;
-    if (m->cfg.num_layers > 0)
-      n = "k_serve5<" + std::to_string(serve5_depth(L)) + ", " + std::to_string(ndt) + ", 2, 2>";
-    else
-      n = "k_serve<2, " + std::to_string(ndt) + ", 4>";
+  } else if (what == 3 && m->serve_choice.form) {
+    n = serve_form_name(*m->serve_choice.form);   // the kernel the last p3d_serve launched
+  } else if (what == 3) {   // before any launch: the form launches no k_serve6 form takes run
+    const int nl = m->cfg.num_layers;
+    n = serve_kernel_name(serve_fallback_kind(nl), serve_fallback_depth(m->cfg.linear_size, nl),
+                          (m->cfg.output_size + 15) / 16, 0, 4, false);
   } else if (what == 2) {
     n = m->train_split ? "k_fwd<1, 8, 8, 2, true, true, 1>" : "k_fwd<4, 8, 8, 2, true, true, 1>";
   } else if (what == 4) {

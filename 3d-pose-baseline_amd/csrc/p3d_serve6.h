@@ -8,7 +8,7 @@
 // (8 hidden phases, each ~20 us) for 1.25 steps of work.  The critical path of a launch of nb
 // steps is (rounds of steps) x (phases) x (column tiles per CU + fixed cost per phase), so
 // k_serve6 takes the groups-per-XCD S as a launch argument, chosen on the host for nb
-// (p3d.hip, serve6_split): at nb = 20, S = 3 groups of 11/11/10 CUs run all 20 steps at once,
+// (p3d_serve_plan.h): at nb = 20, S = 3 groups of 11/11/10 CUs run all 20 steps at once,
 // each CU contracting <= 7 of a layer's 64 column tiles per phase -- 28 16x16 tiles of K = 1024
 // on the critical path and 4 phases, instead of 32 tiles and 8 phases.
 //
@@ -98,7 +98,7 @@ __device__ __forceinline__ int p3d_tile_owner(int t, int n, int T) { return ((t 
 // RT = 6 .. 16 with S = 1 gives each XCD ONE unit of all its rows and all 32 of its CUs, each
 // CU 2 of a layer's 64 column tiles for every row tile (20 steps: 160 rows per XCD, RT = 10):
 // no group idles, no CU holds more tiles than another, and each weight fragment is read by one
-// CU per XCD and serves 10 row tiles (p3d.hip serve6_plan picks the form per launch).
+// CU per XCD and serves 10 row tiles (p3d_serve_plan.h serve_plan picks the form per launch).
 // The epilogue / input-layer work of a chunk, RT x NCM 16 x 16 tiles, is dealt to the waves
 // round-robin: unit u = w + 4 j is row tile u / NCM of column tile u % NCM (UMAX per wave).
 //

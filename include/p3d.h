@@ -320,6 +320,14 @@ int p3d_mpjpe_accum_ex(const float* pred_n, const float* gt_n, int32_t D, const 
  * hidden layer (empty before one ran), 6 = the optimizers' weight source: "packed" (W read from its
  * packed Wd copy, the TF-layout master not written) or "master".  (Measurement plumbing for bench.py.) */
 int p3d_kernel_name(const p3d_model* m, int32_t what, char* out, int64_t out_len);
+/* The kernel p3d_serve (with_loss != 0: p3d_serve_mse) would launch for B rows of a model of this
+ * shape on a device of `cus` compute units, under the P3D_SERVE6* environment as it is at the call:
+ * its name as p3d_kernel_name(3) reports it after that launch, and in shape[5], when non-null,
+ * {groups per XCD (0: not k_serve6), row tiles per unit, column tiles per contraction, ring depth,
+ * units}.  P3D_ERR_ARG where those calls refuse the shape or the launch.  Needs no model and touches
+ * no GPU; the batch <= 4 path of p3d_serve_mse is not modelled. */
+int p3d_serve_plan(const p3d_cfg* cfg, int32_t cus, int64_t B, int32_t with_loss, char* name, int64_t name_len,
+                   int32_t* shape);
 
 /* Host-binding plumbing: a DLPack v0.8 DLManagedTensor aliasing `data` (no copy; the
  * memory stays owned by its model), with a C deleter that frees only the record.  Wrap

@@ -651,3 +651,24 @@ def test_host_wait_reports_instead_of_spinning():
     torch.cuda.synchronize()
     m.check_errors()
     m.close()
+
+
+def test_serve_launches_the_kernel_the_planner_names():
+    """p3d_serve_plan (the planner alone, given the device's CU count) names the kernel each launch
+    runs: a lone request, a ragged few steps, the 20-step launch and a long one, on a narrow model
+    (L 256: no pair form, long launches on k_serve5)."""
+    import ctypes
+    import _p3d
+    cfg = ref_mlp.Cfg(linear_size=256, num_layers=1, residual=True, batch_norm=True)
+    st, m = make(cfg)
+    lib = _p3d.lib()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    pcfg = _p3d.P3DCfg(256, 1, 1, 1, 0, 32, 48, _p3d.P3D_DTYPE_F32, 64, 1e-3, 0.99)
+    for B in (64, 327, 1280, 2049):
+        m.serve_device(torch.zeros((B, 32), device="cuda"))
+        m.serve_check()
+        ran, planned = ctypes.create_string_buffer(128), ctypes.create_string_buffer(128)
+        _p3d.check(lib.p3d_kernel_name(m._h, 3, ran, 128), "p3d_kernel_name")
+        _p3d.check(lib.p3d_serve_plan(ctypes.byref(pcfg), cus, B, 0, planned, 128, None), "p3d_serve_plan")
+        assert ran.value == planned.value, (B, ran.value, planned.value)
+    m.close()
