@@ -2308,14 +2308,21 @@ static int host_errors(p3d_model* m, const char* what) {
   return P3D_OK;
 }
 
+// idx 8 (the *_sync calls): the word must equal the launch's own sequence number.  idx 9
+// (p3d_host_signal's counter, which only advances): a count already passed has been reached too,
+// compared as a wrapping difference.
 static int host_wait(p3d_model* m, unsigned seq, hipStream_t st, const char* what, int idx = 8) {
   unsigned* word = reinterpret_cast<unsigned*>(m->errw) + idx;
+  const auto reached = [&]() {
+    const unsigned w = __atomic_load_n(word, __ATOMIC_ACQUIRE);
+    return idx == 9 ? (int32_t)(w - seq) >= 0 : w == seq;
+  };
   for (uint64_t n = 1;; ++n) {
-    if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) return P3D_OK;
+    if (reached()) return P3D_OK;
     if ((n & 4095) == 0) {
       const hipError_t e = hipStreamQuery(st);
       if (e == hipSuccess) {
-        if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) return P3D_OK;
+        if (reached()) return P3D_OK;
         return fail(P3D_ERR_HIP, std::string(what) + ": the launch completed without storing its completion word");
       }
       if (e != hipErrorNotReady) return fail(P3D_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));

@@ -350,11 +350,14 @@ int p3d_empty_launch(p3d_model* m, int32_t grid, void* stream);
  * session.run returns its fetches; LinearModel.step(isTraining=True) from numpy): p3d_host_signal
  * enqueues one small kernel that advances the model's signal counter and stores the new count into
  * a pinned word (system-scope release); it is capturable, and each replay of a graph holding it
- * signals once.  p3d_host_wait(m, count, stream) returns once the count has reached `count` -- the
+ * signals once.  p3d_host_wait(m, count, stream) returns once the count has reached `count` (a count
+ * already passed included: the 32-bit counter wraps, and the comparison is of the signed difference) -- the
  * kernels before the signal have completed and their writes to coherent host memory are visible --
  * then reports a set kernel error word as P3D_ERR_HIP (p3d_error_flags says which); it polls the
  * stream now and then, so a failed launch is reported instead of waited for.  The stream itself
- * is not synchronised.  p3d_host_alloc / p3d_host_free: coherent pinned host memory (mapped, not
+ * is not synchronised.  A caller waits for the count of its OWN signal: waiting for a smaller count
+ * returns as soon as that earlier signal was stored, whatever is still running behind it.
+ * p3d_host_alloc / p3d_host_free: coherent pinned host memory (mapped, not
  * cached on the device), where kernels' host-memory outputs must live for p3d_host_wait to cover
  * them. */
 int p3d_host_signal(p3d_model* m, void* stream);

@@ -653,6 +653,40 @@ def test_host_wait_reports_instead_of_spinning():
     m.close()
 
 
+def test_host_wait_returns_for_a_count_already_passed():
+    """p3d_host_wait returns once the signal count has REACHED the awaited one (include/p3d.h): after
+    two signals a wait for the first count -- the word is already one past it -- returns P3D_OK, as
+    does the wait for the second; a count nothing was issued for is still reported (P3D_ERR_HIP,
+    "without storing") instead of waited for, and the model keeps working afterwards."""
+    import ctypes
+    import _p3d
+    cfg = ref_mlp.Cfg(linear_size=256, num_layers=1, residual=True, batch_norm=True)
+    st, m = make(cfg)
+    lib = _p3d.lib()
+    sh = ctypes.c_void_p(_p3d.stream_handle())
+    first = (m._hsig + 1) & 0xffffffff
+    second = (m._hsig + 2) & 0xffffffff
+    _p3d.check(lib.p3d_host_signal(m._h, sh), "p3d_host_signal")
+    _p3d.check(lib.p3d_host_signal(m._h, sh), "p3d_host_signal")
+    torch.cuda.synchronize()                    # both stored: the word is past `first`
+    assert lib.p3d_host_wait(m._h, first, sh) == 0, lib.p3d_last_error()
+    assert lib.p3d_host_wait(m._h, second, sh) == 0, lib.p3d_last_error()
+    rc = lib.p3d_host_wait(m._h, (second + 5) & 0xffffffff, sh)
+    assert rc == 2 and b"without storing" in lib.p3d_last_error()
+    # not yet stored when the wait begins: the third signal's count, waited for without a synchronize
+    _p3d.check(lib.p3d_host_signal(m._h, sh), "p3d_host_signal")
+    assert lib.p3d_host_wait(m._h, (second + 1) & 0xffffffff, sh) == 0, lib.p3d_last_error()
+    m._hsig = (second + 1) & 0xffffffff         # (the host mirror step() waits with)
+    rng = np.random.default_rng(3)
+    x, t = rng.standard_normal((64, 32)), rng.standard_normal((64, 48))
+    loss, _, out = m.step(None, x, t, 1.0, isTraining=False)
+    rl, ro = ref_mlp.eval_step(st, x, t)
+    close(out, ro)
+    torch.cuda.synchronize()
+    m.check_errors()
+    m.close()
+
+
 def test_serve_launches_the_kernel_the_planner_names():
     """p3d_serve_plan (the planner alone, given the device's CU count) names the kernel each launch
     runs: a lone request, a ragged few steps, the 20-step launch and a long one, on a narrow model

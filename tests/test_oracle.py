@@ -293,3 +293,47 @@ def test_integer_models_are_exact(L, N, nnz, B):
     out = exact_models.exact_forward(st, x)
     assert float((out != 0).mean()) > 0.5            # not a degenerate all-zero network
     assert np.array_equal(ref_mlp.forward_bf16(st, x, acc=np.float64), ref_mlp.forward_bf16(st, x, acc=np.float32))
+
+
+def _exact_models():
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import exact_models
+    return exact_models
+
+
+@pytest.mark.parametrize("case", sorted(_exact_models().BACKWARD_CASES))
+def test_integer_models_are_exact_in_training(case):
+    """Every shape of the bit-exact training tests (tests/test_gpu_exact.py) really is exact:
+    exact_backward asserts that the oracle's float32 and float64 training forward + backward agree
+    bit for bit, that every gradient is an integer and that the absolute sum of every contraction
+    stays below 2^23; here also that the gradients are dense enough to be a check (a dropped row,
+    k-group or tile changes elements) and that dropout and the row offset really enter."""
+    em = _exact_models()
+    cfg, st, x, dy, keep, row0, out, grads = em.backward_case(case)
+    assert sorted(grads) == sorted(n for n, _ in ref_mlp.param_names(cfg))
+    assert float((out != 0).mean()) > 0.5
+    for name, g in grads.items():
+        # (sparsest: the last block's second layer, whose dz is the 8-per-column dy W4^T under the
+        # ReLU and dropout masks; at 15 % a 16 x 16 tile still holds ~38 non-zero elements)
+        nz = float((g != 0).mean())
+        assert nz > (0.9 if name.split("/")[-1] in ("w1", "w4") else 0.15), (name, nz)
+    if keep < 1.0:   # another call counter or row offset is another mask, and other gradients
+        for ctr, r0 in ((em.BACKWARD_CTR + 1, row0), (em.BACKWARD_CTR, row0 + 1)):
+            o2, _ = ref_mlp.forward(st, x, True, keep, em.BACKWARD_SEED, ctr, r0, dt=np.float32)
+            assert not np.array_equal(o2, out)
+
+
+def test_exact_backward_refuses_inexact_models():
+    """BN (1 / sqrt(var + eps)), max-norm (a Frobenius norm) and a keep whose reciprocal is no power
+    of two are not exact arithmetic: exact_backward refuses them instead of pinning rounding."""
+    em = _exact_models()
+    x, dy = em.integer_inputs(8), em.integer_dy(8, 48)
+    for kw in ({"batch_norm": True}, {"batch_norm": False, "max_norm": True}):
+        cfg, st = em.integer_state(256, 1, batch_norm=kw["batch_norm"])
+        cfg.max_norm = kw.get("max_norm", False)
+        with pytest.raises(AssertionError, match="not exact"):
+            em.exact_backward(st, x, dy, 1.0, 3, 7, 0)
+    cfg, st = em.integer_state(256, 1, batch_norm=False)
+    with pytest.raises(AssertionError, match="power of two"):
+        em.exact_backward(st, x, dy, 0.75, 3, 7, 0)
+    em.exact_backward(st, x, dy, 0.5, 3, 7, 0)
