@@ -121,6 +121,30 @@ SIGNATURES = [
     ("p3d_dp_attach", c_int32, [c_void_p, c_void_p]),
     ("p3d_train_step_dp", c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_float, c_uint64, c_int64,
                                     c_float, c_float, c_float, c_void_p, c_void_p]),
+    ("p3d_vae_create", c_int32, [c_int32, c_int32, POINTER(c_int32), c_int32, c_int32, POINTER(c_int32), c_int32,
+                                 c_int32, c_uint64, POINTER(c_void_p)]),
+    ("p3d_vae_destroy", c_int32, [c_void_p]),
+    ("p3d_vae_lds_bytes", c_int64, [c_int32, c_int32, POINTER(c_int32), c_int32, c_int32, POINTER(c_int32), c_int32]),
+    ("p3d_vae_param_count", c_int32, [c_void_p, POINTER(c_int32)]),
+    ("p3d_vae_param_info", c_int32, [c_void_p, c_int32, POINTER(c_char_p), POINTER(c_int64), POINTER(c_int32),
+                                     POINTER(c_int32), POINTER(c_int64)]),
+    ("p3d_vae_param_ptr", c_int32, [c_void_p, c_char_p, POINTER(c_void_p), POINTER(c_int64)]),
+    ("p3d_vae_flat_ptr", c_int32, [c_void_p, c_int32, POINTER(c_void_p), POINTER(c_int64)]),
+    ("p3d_vae_params_updated", c_int32, [c_void_p, c_void_p]),
+    ("p3d_vae_forward", c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("p3d_vae_loss", c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_uint64, POINTER(c_float),
+                               c_void_p, c_void_p]),
+    ("p3d_vae_grad", c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_uint64, POINTER(c_float),
+                               c_void_p, c_void_p]),
+    ("p3d_vae_train_step", c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_float), c_float,
+                                     c_void_p, c_void_p]),
+    ("p3d_vae_adam_apply", c_int32, [c_void_p, c_float, c_void_p]),
+    ("p3d_vae_set_form", c_int32, [c_void_p, c_int32]),
+    ("p3d_vae_get_step", c_int32, [c_void_p, POINTER(c_int64), POINTER(c_float), POINTER(c_float)]),
+    ("p3d_vae_set_step", c_int32, [c_void_p, c_int64, c_float, c_float]),
+    ("p3d_vae_eps", c_int32, [c_uint64, c_uint64, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
+    ("p3d_vae_workspace", c_int64, [c_void_p, c_int64]),
 ]
 
 

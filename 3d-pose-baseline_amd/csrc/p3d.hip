@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "p3d_layers.h"
+#include "p3d_vae.h"
 
 // =====================================================================================
 // host side
@@ -2596,6 +2597,393 @@ extern "C" uint32_t p3d_crc32c(const void* data, int64_t n, uint32_t crc) {
   }
   while (n-- > 0) c = (c >> 8) ^ tb.t[0][(c ^ *p++) & 0xFFu];
   return ~c;
+}
+
+// =====================================================================================
+// The VAE pose filter (include/p3d.h; kernels in p3d_vae.h)
+// =====================================================================================
+struct p3d_vae {
+  VaeDesc desc{};
+  std::vector<std::string> names;       // Keras order; tensor i is desc.T[i]
+  int max_batch = 0, form = 0, cus = 0;
+  uint64_t seed = 0;
+  size_t lds = 0;                       // dynamic LDS bytes of k_vae_fwd / k_vae_step
+  int64_t ws_floats = 0;
+  VaeDesc* d_desc = nullptr;
+  float* params = nullptr; float* grads = nullptr; float* am = nullptr; float* av = nullptr;
+  float* pk = nullptr; float* ws = nullptr;
+  int* pkidx = nullptr;                 // flat element -> packed copy (device)
+  VaeState* st = nullptr;
+};
+
+namespace {
+
+int ceil16(int n) { return (n + 15) / 16 * 16; }
+
+// The layout of a filter (host only): layers, the packed copy, a wave's LDS area, the master
+// tensors.  wpad = 4 staggers the packed rows over the LDS banks for the data-gradient reads;
+// 0 is the fall-back when that does not fit; stage_x keeps the 16-row input tile in LDS too (else
+// layer 0 reads x from global memory).  Returns the dynamic LDS bytes.
+size_t vae_layout(VaeDesc& d, std::vector<std::string>& names, int in, int n_enc, const int32_t* enc, int latent,
+                  int n_dec, const int32_t* dec, int out, int wpad, int stage_x) {
+  d = VaeDesc{};
+  names.clear();
+  d.in = in; d.latent = latent; d.out = out;
+  int pk = 0, act = 0, flat = 0, prev = in;
+  auto tensor = [&](const std::string& name, int K, int N, int pkoff, int ld) {
+    d.T[d.nt++] = VaeTensor{flat, K, N, pkoff, ld};
+    names.push_back(name);
+    flat += K * N;
+    return flat - K * N;
+  };
+  auto layer = [&](int K, int N, int relu) -> VaeLayer& {
+    VaeLayer& L = d.L[d.nl++];
+    L.K = K; L.N = N; L.Np = ceil16(N); L.ld = L.Np + wpad; L.relu = relu;
+    L.wpk = pk; pk += K * L.ld;
+    L.bpk = pk; pk += L.Np;
+    L.aout = act; L.ldo = L.Np + 2; act += 16 * L.ldo;
+    L.split = N; L.fw2 = L.fb2 = 0;
+    return L;
+  };
+  for (int e = 0; e < n_enc; ++e) {
+    VaeLayer& L = layer(prev, enc[e], 1);
+    const std::string s = "enc_h_" + std::to_string(enc[e]);
+    L.fw = tensor(s + "/kernel", L.K, L.N, L.wpk, L.ld);
+    L.fb = tensor(s + "/bias", 1, L.N, L.bpk, L.Np);
+    prev = enc[e];
+  }
+  {
+    d.head = d.nl;
+    VaeLayer& L = layer(prev, 2 * latent, 0);
+    L.split = latent;
+    L.fw = tensor("mean/kernel", L.K, latent, L.wpk, L.ld);
+    L.fb = tensor("mean/bias", 1, latent, L.bpk, L.Np);
+    L.fw2 = tensor("log_varianze/kernel", L.K, latent, L.wpk + latent, L.ld);
+    L.fb2 = tensor("log_varianze/bias", 1, latent, L.bpk + latent, L.Np);
+    prev = latent;
+  }
+  for (int e = 0; e <= n_dec; ++e) {
+    const int N = e < n_dec ? dec[e] : out;
+    VaeLayer& L = layer(prev, N, e < n_dec);
+    const std::string s = e < n_dec ? "dec_f_" + std::to_string(N) : std::string("dec_f_out");
+    L.fw = tensor(s + "/kernel", L.K, L.N, L.wpk, L.ld);
+    L.fb = tensor(s + "/bias", 1, L.N, L.bpk, L.Np);
+    prev = N;
+  }
+  d.ldz = ceil16(latent) + 2; d.zbuf = act; act += 16 * d.ldz;
+  d.lde = d.ldz; d.ebuf = act; act += 16 * d.lde;
+  d.ldb = 50; d.bt = act;
+  if (out == 48) act += 16 * d.ldb;
+  d.ldx = ceil16(in) + 2; d.xbuf = -1;
+  if (stage_x) { d.xbuf = act; act += 16 * d.ldx; }
+  for (int l = 0; l < d.nl; ++l) {
+    VaeLayer& L = d.L[l];
+    if (l == 0) { L.ain = d.xbuf; L.lda = d.xbuf >= 0 ? d.ldx : in; }
+    else if (l == d.head + 1) { L.ain = d.zbuf; L.lda = d.ldz; }
+    else { L.ain = d.L[l - 1].aout; L.lda = d.L[l - 1].ldo; }
+  }
+  d.P = flat;
+  d.Ppk = (pk + 3) / 4 * 4;
+  d.act = (act + 3) / 4 * 4;
+  return sizeof(float) * ((size_t)d.Ppk + 4 * (size_t)d.act + 64 * 4);
+}
+
+// the roomiest layout that fits one workgroup's LDS (else the last one's size, over the limit)
+size_t vae_best_layout(VaeDesc& d, std::vector<std::string>& names, int in, int n_enc, const int32_t* enc, int latent,
+                       int n_dec, const int32_t* dec, int out) {
+  const int tries[3][2] = {{4, 1}, {4, 0}, {0, 0}};
+  size_t lds = 0;
+  for (auto& t : tries) {
+    lds = vae_layout(d, names, in, n_enc, enc, latent, n_dec, dec, out, t[0], t[1]);
+    if (lds <= P3D_VAE_LDS_LIMIT) break;
+  }
+  return lds;
+}
+
+int vae_check_call(const p3d_vae* v, const float* x, int64_t B, const char* what) {
+  if (!v || !x) return fail(P3D_ERR_ARG, std::string(what) + ": null argument");
+  if (B < 1 || B > (1 << 20)) return fail(P3D_ERR_ARG, std::string(what) + ": B must be in 1 .. 2^20");
+  return P3D_OK;
+}
+
+VaeArgs vae_args(const p3d_vae* v, const float* x, const float* t, int64_t B, const float* eps, uint64_t ctr) {
+  VaeArgs a{};
+  a.desc = v->d_desc; a.pk = v->pk; a.x = x; a.t = t; a.eps = eps; a.B = B;
+  a.seed = v->seed; a.ctr = ctr;
+  a.ctr_dev = ctr == P3D_CTR_GLOBAL_STEP ? v->st : nullptr;
+  a.w = v->params; a.m = v->am; a.v = v->av; a.pk_out = v->pk; a.st = v->st;
+  a.pkidx = v->pkidx;
+  a.nblk = 1;
+  return a;
+}
+
+// loss (backward = 0), gradient (backward = 1) or training step (adam = 1) over B rows
+int vae_step(p3d_vae* v, const float* x, const float* t, int64_t B, const float* eps, uint64_t ctr,
+             const float* factors, int backward, int adam, float lr, float* loss3, void* stream,
+             const char* what) {
+  if (int rc = vae_check_call(v, x, B, what)) return rc;
+  if (!t || !factors || !loss3) return fail(P3D_ERR_ARG, std::string(what) + ": null argument");
+  if (B > v->max_batch) return fail(P3D_ERR_ARG, std::string(what) + ": B exceeds max_batch");
+  if (factors[1] != 0.0f && v->desc.out != 48)
+    return fail(P3D_ERR_ARG, std::string(what) + ": the KCS term needs out == 48 (kcs_factor must be 0)");
+  VaeArgs a = vae_args(v, x, t, B, eps, ctr);
+  const int nblk = (int)((B + 63) / 64);
+  const bool one = nblk == 1 && v->form == 0;
+  a.backward = backward; a.adam = adam; a.lr = lr;
+  a.nblk = nblk;
+  a.c_like = (float)(2.0 * (double)factors[0] / ((double)B * v->desc.out));
+  a.c_kcs = (float)((double)factors[1] / (double)B);
+  a.c_kl = (float)((double)factors[2] / (double)B);
+  for (int j = 0; j < 3; ++j) a.f[j] = factors[j];
+  a.lpart = v->ws + (int64_t)nblk * v->desc.P;
+  a.loss3 = loss3;
+  a.gout = one ? v->grads : v->ws;
+  a.tail = one;
+  const hipStream_t st = (hipStream_t)stream;
+  const int grid = nblk < v->cus ? nblk : v->cus;
+  hipLaunchKernelGGL(k_vae_step, dim3(grid), dim3(256), v->lds, st, a);
+  LAUNCH_CHECK("k_vae_step");
+  if (one) return P3D_OK;
+  // the partials form: block sums (gradient and loss) and the optimizer, behind it on the stream
+  hipLaunchKernelGGL(k_vae_reduce_adam, dim3(backward ? (v->desc.P + 255) / 256 : 1), dim3(256), 0, st, a, v->grads);
+  LAUNCH_CHECK("k_vae_reduce_adam");
+  return P3D_OK;
+}
+
+}  // namespace
+
+namespace {
+int vae_check_shape(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent, int32_t n_dec,
+                    const int32_t* dec_dims, int32_t out) {
+  if (!enc_dims || !dec_dims) return fail(P3D_ERR_ARG, "p3d_vae_create: null argument");
+  auto width = [](int w, int hi) { return w >= 8 && w <= hi && w % 8 == 0; };
+  if (!width(in, 256)) return fail(P3D_ERR_ARG, "p3d_vae_create: in must be a multiple of 8 in 8 .. 256");
+  if (n_enc < 1 || n_enc > 4 || n_dec < 1 || n_dec > 4)
+    return fail(P3D_ERR_ARG, "p3d_vae_create: 1 to 4 hidden layers on each side");
+  for (int e = 0; e < n_enc; ++e)
+    if (!width(enc_dims[e], 256)) return fail(P3D_ERR_ARG, "p3d_vae_create: hidden widths must be multiples of 8 in 8 .. 256");
+  for (int e = 0; e < n_dec; ++e)
+    if (!width(dec_dims[e], 256)) return fail(P3D_ERR_ARG, "p3d_vae_create: hidden widths must be multiples of 8 in 8 .. 256");
+  if (!width(latent, 64)) return fail(P3D_ERR_ARG, "p3d_vae_create: latent must be a multiple of 8 in 8 .. 64");
+  if (!width(out, 64)) return fail(P3D_ERR_ARG, "p3d_vae_create: out must be a multiple of 8 in 8 .. 64");
+  return P3D_OK;
+}
+}  // namespace
+
+extern "C" int64_t p3d_vae_lds_bytes(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent, int32_t n_dec,
+                                     const int32_t* dec_dims, int32_t out) {
+  if (vae_check_shape(in, n_enc, enc_dims, latent, n_dec, dec_dims, out)) return 0;
+  VaeDesc d;
+  std::vector<std::string> names;
+  return (int64_t)vae_best_layout(d, names, in, n_enc, enc_dims, latent, n_dec, dec_dims, out);
+}
+
+extern "C" int p3d_vae_create(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent, int32_t n_dec,
+                              const int32_t* dec_dims, int32_t out, int32_t max_batch, uint64_t seed, p3d_vae** vout) {
+  if (!vout) return fail(P3D_ERR_ARG, "p3d_vae_create: null argument");
+  if (int rc = vae_check_shape(in, n_enc, enc_dims, latent, n_dec, dec_dims, out)) return rc;
+  if (max_batch < 1 || max_batch > (1 << 20)) return fail(P3D_ERR_ARG, "p3d_vae_create: max_batch must be in 1 .. 2^20");
+  p3d_vae* v = new p3d_vae();
+  v->lds = vae_best_layout(v->desc, v->names, in, n_enc, enc_dims, latent, n_dec, dec_dims, out);
+  if (v->lds > P3D_VAE_LDS_LIMIT) {
+    const size_t need = v->lds;
+    delete v;
+    return fail(P3D_ERR_ARG, "p3d_vae_create: parameters and working space need " + std::to_string(need) +
+                                 " bytes of LDS, a workgroup has " + std::to_string(P3D_VAE_LDS_LIMIT));
+  }
+  for (size_t i = 0; i < v->names.size(); ++i)
+    for (size_t j = 0; j < i; ++j)
+      if (v->names[i] == v->names[j]) {   // keras: "All layers added to a Model must have unique names"
+        const std::string dup = v->names[i];
+        delete v;
+        return fail(P3D_ERR_ARG, "p3d_vae_create: two layers of one side share the width in " + dup +
+                                     " (keras layer names must be unique)");
+      }
+  v->max_batch = max_batch;
+  v->seed = seed;
+  const int64_t nblk = (max_batch + 63) / 64;
+  v->ws_floats = nblk * ((int64_t)v->desc.P + 4) + 4;
+  auto bail = [&](hipError_t e, const char* what) {
+    p3d_vae_destroy(v);
+    return fail(P3D_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+  };
+  hipError_t e;
+  int dev = 0;
+  if ((e = hipGetDevice(&dev)) != hipSuccess) return bail(e, "hipGetDevice");
+  hipDeviceProp_t prop;
+  if ((e = hipGetDeviceProperties(&prop, dev)) != hipSuccess) return bail(e, "hipGetDeviceProperties");
+  v->cus = prop.multiProcessorCount;
+  const size_t pb = sizeof(float) * (size_t)v->desc.P;
+  float** bufs[4] = {&v->params, &v->grads, &v->am, &v->av};
+  for (auto b : bufs) {
+    if ((e = hipMalloc((void**)b, pb)) != hipSuccess) return bail(e, "hipMalloc");
+    if ((e = hipMemset(*b, 0, pb)) != hipSuccess) return bail(e, "hipMemset");
+  }
+  if ((e = hipMalloc((void**)&v->pk, sizeof(float) * v->desc.Ppk)) != hipSuccess) return bail(e, "hipMalloc");
+  if ((e = hipMemset(v->pk, 0, sizeof(float) * v->desc.Ppk)) != hipSuccess) return bail(e, "hipMemset");
+  if ((e = hipMalloc((void**)&v->ws, sizeof(float) * v->ws_floats)) != hipSuccess) return bail(e, "hipMalloc");
+  if ((e = hipMemset(v->ws, 0, sizeof(float) * v->ws_floats)) != hipSuccess) return bail(e, "hipMemset");
+  if ((e = hipMalloc((void**)&v->d_desc, sizeof(VaeDesc))) != hipSuccess) return bail(e, "hipMalloc");
+  if ((e = hipMemcpy(v->d_desc, &v->desc, sizeof(VaeDesc), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
+  {
+    std::vector<int> idx((size_t)v->desc.P);
+    for (int t = 0; t < v->desc.nt; ++t) {
+      const VaeTensor& T = v->desc.T[t];
+      for (int k = 0; k < T.K; ++k)
+        for (int n = 0; n < T.N; ++n) idx[(size_t)T.flat + (size_t)k * T.N + n] = T.pk + k * T.ld + n;
+    }
+    if ((e = hipMalloc((void**)&v->pkidx, sizeof(int) * idx.size())) != hipSuccess) return bail(e, "hipMalloc");
+    if ((e = hipMemcpy(v->pkidx, idx.data(), sizeof(int) * idx.size(), hipMemcpyHostToDevice)) != hipSuccess)
+      return bail(e, "hipMemcpy");
+  }
+  if ((e = hipMalloc((void**)&v->st, sizeof(VaeState))) != hipSuccess) return bail(e, "hipMalloc");
+  const VaeState s0{0, 0.9f, 0.999f, 0.0f, {0, 0, 0}};
+  if ((e = hipMemcpy(v->st, &s0, sizeof(VaeState), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
+  if ((e = hipFuncSetAttribute((const void*)k_vae_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->lds)) != hipSuccess)
+    return bail(e, "hipFuncSetAttribute(k_vae_fwd)");
+  if ((e = hipFuncSetAttribute((const void*)k_vae_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->lds)) != hipSuccess)
+    return bail(e, "hipFuncSetAttribute(k_vae_step)");
+  *vout = v;
+  return P3D_OK;
+}
+
+extern "C" int p3d_vae_destroy(p3d_vae* v) {
+  if (!v) return P3D_OK;
+  void* bufs[] = {v->params, v->grads, v->am, v->av, v->pk, v->ws, v->d_desc, v->st, v->pkidx};
+  for (void* b : bufs)
+    if (b) (void)hipFree(b);
+  delete v;
+  return P3D_OK;
+}
+
+extern "C" int p3d_vae_param_count(const p3d_vae* v, int32_t* count) {
+  if (!v || !count) return fail(P3D_ERR_ARG, "p3d_vae_param_count: null argument");
+  *count = v->desc.nt;
+  return P3D_OK;
+}
+
+extern "C" int p3d_vae_param_info(const p3d_vae* v, int32_t idx, const char** name, int64_t* numel, int32_t* rows,
+                                  int32_t* cols, int64_t* offset) {
+  if (!v) return fail(P3D_ERR_ARG, "p3d_vae_param_info: null argument");
+  if (idx < 0 || idx >= v->desc.nt) return fail(P3D_ERR_ARG, "p3d_vae_param_info: index out of range");
+  const VaeTensor& T = v->desc.T[idx];
+  if (name) *name = v->names[idx].c_str();
+  if (numel) *numel = (int64_t)T.K * T.N;
+  if (rows) *rows = T.K;
+  if (cols) *cols = T.N;
+  if (offset) *offset = T.flat;
+  return P3D_OK;
+}
+
+extern "C" int p3d_vae_param_ptr(p3d_vae* v, const char* name, void** dptr, int64_t* numel) {
+  if (!v || !name || !dptr) return fail(P3D_ERR_ARG, "p3d_vae_param_ptr: null argument");
+  for (int i = 0; i < v->desc.nt; ++i)
+    if (v->names[i] == name) {
+      *dptr = v->params + v->desc.T[i].flat;
+      if (numel) *numel = (int64_t)v->desc.T[i].K * v->desc.T[i].N;
+      return P3D_OK;
+    }
+  return fail(P3D_ERR_NOTFOUND, std::string("p3d_vae_param_ptr: no parameter named ") + name);
+}
+
+extern "C" int p3d_vae_flat_ptr(p3d_vae* v, int32_t which, void** dptr, int64_t* numel) {
+  if (!v || !dptr) return fail(P3D_ERR_ARG, "p3d_vae_flat_ptr: null argument");
+  float* const bufs[6] = {v->params, v->grads, v->am, v->av, v->ws, v->pk};
+  if (which < 0 || which > 5) return fail(P3D_ERR_ARG, "p3d_vae_flat_ptr: which must be 0 .. 5");
+  *dptr = bufs[which];
+  if (numel) *numel = which == 4 ? v->ws_floats : which == 5 ? v->desc.Ppk : v->desc.P;
+  return P3D_OK;
+}
+
+extern "C" int p3d_vae_params_updated(p3d_vae* v, void* stream) {
+  if (!v) return fail(P3D_ERR_ARG, "p3d_vae_params_updated: null argument");
+  hipLaunchKernelGGL(k_vae_pack, dim3((v->desc.P + 255) / 256), dim3(256), 0, (hipStream_t)stream, v->desc.P,
+                     (const int*)v->pkidx, (const float*)v->params, v->pk);
+  LAUNCH_CHECK("k_vae_pack");
+  return P3D_OK;
+}
+
+extern "C" int p3d_vae_forward(p3d_vae* v, const float* x, int64_t B, const float* eps, uint64_t ctr, float* y,
+                               float* mean, float* log_var, float* z, const float* target, float* row_terms,
+                               void* stream) {
+  if (int rc = vae_check_call(v, x, B, "p3d_vae_forward")) return rc;
+  if ((row_terms != nullptr) != (target != nullptr))
+    return fail(P3D_ERR_ARG, "p3d_vae_forward: row_terms and target go together");
+  VaeArgs a = vae_args(v, x, target, B, eps, ctr);
+  a.y = y; a.mean = mean; a.log_var = log_var; a.z = z; a.row_terms = row_terms;
+  const int64_t nwg = (B + 63) / 64;
+  const int grid = (int)(nwg < v->cus ? nwg : v->cus);
+  hipLaunchKernelGGL(k_vae_fwd, dim3(grid), dim3(256), v->lds, (hipStream_t)stream, a);
+  LAUNCH_CHECK("k_vae_fwd");
+  return P3D_OK;
+}
+
+extern "C" int p3d_vae_loss(p3d_vae* v, const float* x, const float* t, int64_t B, const float* eps, uint64_t ctr,
+                            const float* factors, float* loss3_dev, void* stream) {
+  return vae_step(v, x, t, B, eps, ctr, factors, 0, 0, 0.0f, loss3_dev, stream, "p3d_vae_loss");
+}
+
+extern "C" int p3d_vae_grad(p3d_vae* v, const float* x, const float* t, int64_t B, const float* eps, uint64_t ctr,
+                            const float* factors, float* loss3_dev, void* stream) {
+  return vae_step(v, x, t, B, eps, ctr, factors, 1, 0, 0.0f, loss3_dev, stream, "p3d_vae_grad");
+}
+
+extern "C" int p3d_vae_train_step(p3d_vae* v, const float* x, const float* t, int64_t B, const float* eps,
+                                  const float* factors, float lr, float* loss3_dev, void* stream) {
+  if (!(lr >= 0.0f)) return fail(P3D_ERR_ARG, "p3d_vae_train_step: lr must be >= 0");
+  return vae_step(v, x, t, B, eps, P3D_CTR_GLOBAL_STEP, factors, 1, 1, lr, loss3_dev, stream, "p3d_vae_train_step");
+}
+
+extern "C" int p3d_vae_adam_apply(p3d_vae* v, float lr, void* stream) {
+  if (!v || !(lr >= 0.0f)) return fail(P3D_ERR_ARG, "p3d_vae_adam_apply: bad argument");
+  VaeArgs a = vae_args(v, nullptr, nullptr, 1, nullptr, 0);
+  a.backward = 1; a.adam = 1; a.nblk = 1; a.gout = v->grads; a.loss3 = nullptr;
+  hipLaunchKernelGGL(k_vae_alpha, dim3(1), dim3(1), 0, (hipStream_t)stream, v->st, lr);
+  LAUNCH_CHECK("k_vae_alpha");
+  hipLaunchKernelGGL(k_vae_reduce_adam, dim3((v->desc.P + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, v->grads);
+  LAUNCH_CHECK("k_vae_reduce_adam");
+  return P3D_OK;
+}
+
+extern "C" int p3d_vae_set_form(p3d_vae* v, int32_t form) {
+  if (!v || (form != 0 && form != 1)) return fail(P3D_ERR_ARG, "p3d_vae_set_form: form must be 0 or 1");
+  v->form = form;
+  return P3D_OK;
+}
+
+extern "C" int p3d_vae_get_step(const p3d_vae* v, int64_t* step, float* beta1_power, float* beta2_power) {
+  if (!v) return fail(P3D_ERR_ARG, "p3d_vae_get_step: null argument");
+  VaeState s;
+  HIP_TRY(hipMemcpy(&s, v->st, sizeof(s), hipMemcpyDeviceToHost));
+  if (step) *step = s.step;
+  if (beta1_power) *beta1_power = s.b1p;
+  if (beta2_power) *beta2_power = s.b2p;
+  return P3D_OK;
+}
+
+extern "C" int p3d_vae_set_step(p3d_vae* v, int64_t step, float beta1_power, float beta2_power) {
+  if (!v || step < 0) return fail(P3D_ERR_ARG, "p3d_vae_set_step: bad argument");
+  const VaeState s{step, beta1_power, beta2_power, 0.0f, {0, 0, 0}};
+  HIP_TRY(hipMemcpy(v->st, &s, sizeof(s), hipMemcpyHostToDevice));
+  return P3D_OK;
+}
+
+extern "C" int p3d_vae_eps(uint64_t seed, uint64_t ctr, int64_t row0, int64_t B, int32_t latent, float* out,
+                           void* stream) {
+  if (!out) return fail(P3D_ERR_ARG, "p3d_vae_eps: null argument");
+  if (B < 1 || B > (1 << 20) || row0 < 0) return fail(P3D_ERR_ARG, "p3d_vae_eps: B must be in 1 .. 2^20, row0 >= 0");
+  if (latent < 4 || latent > 64 || latent % 4 != 0) return fail(P3D_ERR_ARG, "p3d_vae_eps: latent must be a multiple of 4 in 4 .. 64");
+  const int64_t units = B * (latent / 4);
+  hipLaunchKernelGGL(k_vae_eps, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seed, ctr,
+                     row0, B, (int)latent, out);
+  LAUNCH_CHECK("k_vae_eps");
+  return P3D_OK;
+}
+
+extern "C" int64_t p3d_vae_workspace(const p3d_vae* v, int64_t B) {
+  if (!v || B < 1) return 0;
+  const int64_t nblk = (B + 63) / 64;
+  return (int64_t)sizeof(float) * (nblk * ((int64_t)v->desc.P + 4) + 4);
 }
 
 #include "p3d_dp.h"

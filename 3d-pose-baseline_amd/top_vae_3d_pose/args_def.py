@@ -1,0 +1,82 @@
+"""FLAGS shared by the VAE filter's modules (src/top_vae_3d_pose/args_def.py): the reference's names
+and defaults for every flag this build reads, plus ``reaload_from_config_file`` for a settings file
+shaped like src/train.yml (sections of ``key: value`` pairs).  The reference's spelling is kept."""
+import argparse
+import os
+
+BAR_FORMAT = '{l_bar}{bar:30}{r_bar}'
+
+
+def build_parser():
+    p = argparse.ArgumentParser()
+    p.add_argument("--learning_rate", type=float, default=0.001, help="Learning rate")
+    p.add_argument("--dropout", type=float, default=1, help="Dropout keep probability. 1 means no dropout")
+    p.add_argument("--batch_size", type=int, default=64, help="Batch size to use during training")
+    p.add_argument("--epochs", type=int, default=200, help="How many epochs we should train for")
+    p.add_argument("--camera_frame", action='store_true', default=False, help="Convert 3d poses to camera coordinates")
+    p.add_argument("--batch_norm", action='store_true', default=False, help="Use batch_normalization")
+    p.add_argument("--predict_14", action='store_true', default=False, help="predict 14 joints")
+    p.add_argument("--use_sh", action='store_true', default=False, help="Use 2d pose predictions from StackedHourglass")
+    p.add_argument("--action", type=str, default="All", help="The action to train on. 'All' means all the actions")
+    p.add_argument("--optimizer", type=str, default="adam", help="Optimizer to use [adam, rmsprop]")
+    p.add_argument("--model", type=str, default='VAE', help="Model to use: [VAE], default VAE.")
+    p.add_argument("--latent_dim", type=int, default=24, help="VAE latent dimension")
+    p.add_argument("--enc_dim", type=int, nargs='+', default=[40, 32], help="VAE encoder dimension")
+    p.add_argument("--dec_dim", type=int, nargs='+', default=[32, 40], help="VAE decoder dimension")
+    p.add_argument("--step_log", type=int, default=1000, help="Steps between training-loss lines")
+    p.add_argument("--likelihood_factor", type=float, default=1.0, help="Term to regularize the likelihood loss for ELBO")
+    p.add_argument("--dkl_factor", type=float, default=1.0, help="Term to regularize the likelihood loss for ELBO")
+    p.add_argument("--kcs_factor", type=float, default=1.0, help="Term to regularize the likelihood loss for ELBO")
+    p.add_argument("--max_norm", action='store_true', default=False, help="Apply maxnorm constraint to the weights")
+    p.add_argument("--residual", action='store_true', default=False,
+                   help="Whether to add a residual connection every 2 layers")
+    p.add_argument("--train_all", action='store_true', default=False, help="Train all the nn or only the vae nn")
+    p.add_argument("--cameras_path", type=str, default="data/h36m/cameras.h5", help="Directory to load camera parameters")
+    p.add_argument("--data_dir", type=str, default="data/h36m/", help="Data directory")
+    p.add_argument("--train_dir", type=str, default="experiments", help="Training directory.")
+    p.add_argument("--cfg_file", type=str, default="src/train.yml",
+                   help="Config file, the values passed through args are remplaced by the specified in the file")
+    p.add_argument("--sample", action='store_true', default=False, help="Set to True for sampling.")
+    p.add_argument("--load", type=int, default=0, help="Try to load a previous checkpoint.")
+    p.add_argument("--verbose", type=int, default=2, help="0:Error, 1:Warning, 2:INFO*(default), 3:debug")
+    # build-specific: the frozen lifter (the reference hard-codes PoseBase and its checkpoint path)
+    p.add_argument("--linear_size", type=int, default=1024, help="Lifter: size of each model layer")
+    p.add_argument("--num_layers", type=int, default=2, help="Lifter: number of two_linear blocks")
+    p.add_argument("--lifter_dir", type=str, default=None,
+                   help="Lifter: the directory holding checkpoint-<load> (a predict_3dpose.train run's directory)")
+    p.add_argument("--seed", type=int, default=0, help="Weight / eps seed")
+    return p
+
+
+class _ENV(object):
+    def __init__(self):
+        self.BAR_FORMAT = BAR_FORMAT
+        self._parser = build_parser()
+        self.FLAGS = self._parser.parse_args([])     # defaults until setup()
+        self.TRAIN_DIR = None
+        self.SUMMARIES_DIR = None
+
+    def setup(self, read_from_config=False, argv=None):
+        """Set the FLAGS (src/top_vae_3d_pose/args_def.py:112-137)."""
+        self.FLAGS = self._parser.parse_args(argv)
+        f = self.FLAGS
+        self.TRAIN_DIR = os.path.join(f.train_dir, f.action, '{0}_top_model'.format(f.model),
+                                      'dropout_{0}'.format(f.dropout),
+                                      'epochs_{0}'.format(f.epochs) if f.epochs > 0 else '',
+                                      'lr_{0}'.format(f.learning_rate), 'batch_size_{0}'.format(f.batch_size))
+        self.SUMMARIES_DIR = os.path.join(self.TRAIN_DIR, "log")
+        if read_from_config:
+            self.reaload_from_config_file()
+        return self.FLAGS
+
+    def reaload_from_config_file(self):
+        """Read the config file into FLAGS: every key of every section (args_def.py:139-146)."""
+        import yaml
+        with open(self.FLAGS.cfg_file) as fyml:
+            cfg = yaml.safe_load(fyml)
+        for _, data in (cfg or {}).items():
+            for key, value in data.items():
+                setattr(self.FLAGS, key, value)
+
+
+ENVIRON = _ENV()

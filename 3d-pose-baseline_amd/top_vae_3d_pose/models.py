@@ -1,0 +1,294 @@
+"""The VAE pose filter and the lifter + filter model (src/top_vae_3d_pose/models.py:12-91 VAE,
+:485-540 Pose3DVae) over libp3d.so's p3d_vae_* entry points (csrc/p3d_vae.h).
+
+The reference's names are kept so that its scripts drop in.  Everything runs on the GPU; there is
+no CPU fallback.  tf.random.normal's stream cannot be reproduced: eps comes from the library's
+Philox stream (keyed by the model's seed, a call counter, the row and the column), or from the
+caller (``eps=``).
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+import _p3d
+from _p3d import check, lib, ptr
+
+HUMAN_3D_SIZE = 48
+HUMAN_2D_SIZE = 32
+
+
+class VAE(object):
+    """Variational autoencoder input_size -> enc_dim -> {mean, log_varianze} -> dec_dim -> human_3d_size."""
+
+    def __init__(self, input_size, latent_dim, enc_dim, dec_dim, human_3d_size=HUMAN_3D_SIZE, *, max_batch=4096,
+                 seed=None, device=None, init=True):
+        import torch
+
+        self.input_size = int(input_size)
+        self.latent_dim = int(latent_dim)
+        self.enc_dim = [int(u) for u in enc_dim]
+        self.dec_dim = [int(u) for u in dec_dim]
+        self.human_3d_size = int(human_3d_size)
+        self.max_batch = int(max_batch)
+        self.seed = int(seed if seed is not None else np.random.SeedSequence().entropy % (2 ** 63))
+        self.torch = torch
+        self._h = None
+        enc = (ctypes.c_int32 * max(len(self.enc_dim), 1))(*self.enc_dim)
+        dec = (ctypes.c_int32 * max(len(self.dec_dim), 1))(*self.dec_dim)
+        h = ctypes.c_void_p()
+        args = (self.input_size, len(self.enc_dim), enc, self.latent_dim, len(self.dec_dim), dec,
+                self.human_3d_size, self.max_batch, self.seed, ctypes.byref(h))
+        if torch.cuda.is_available():
+            self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+            with torch.cuda.device(self.device):
+                check(lib().p3d_vae_create(*args), "p3d_vae_create")
+        else:   # argument errors answer without a GPU; a valid shape then fails on the missing device
+            rc = lib().p3d_vae_create(*args)
+            if rc == _p3d.P3D_ERR_ARG:
+                check(rc, "p3d_vae_create")
+            raise _p3d.P3DError("VAE needs a ROCm GPU (torch.cuda.is_available() is False); "
+                                "the HIP path has no CPU fallback")
+        self._h = h
+        n = ctypes.c_int32()
+        check(lib().p3d_vae_param_count(self._h, ctypes.byref(n)), "p3d_vae_param_count")
+        self.param_table = []   # (name, shape, offset) in keras order
+        for i in range(n.value):
+            name, numel, rows, cols, off = (ctypes.c_char_p(), ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int32(),
+                                            ctypes.c_int64())
+            check(lib().p3d_vae_param_info(self._h, i, ctypes.byref(name), ctypes.byref(numel), ctypes.byref(rows),
+                                           ctypes.byref(cols), ctypes.byref(off)), "p3d_vae_param_info")
+            nm = name.value.decode()
+            shape = (cols.value,) if nm.endswith("/bias") else (rows.value, cols.value)
+            self.param_table.append((nm, shape, off.value))
+        self._flat = {}
+        self._loss = torch.zeros(3, dtype=torch.float32, device=self.device)
+        self._calls = 0     # eps counter of inference calls
+        if init:
+            self.initialize(self.seed)
+
+    # ------------------------------------------------------------------ plumbing
+    def stream(self):
+        return _p3d.stream_handle()
+
+    def flat(self, which):
+        """Zero-copy view of a flat device buffer: 'params', 'grads', 'adam_m', 'adam_v',
+        'workspace', 'packed'."""
+        idx = ("params", "grads", "adam_m", "adam_v", "workspace", "packed").index(which)
+        if idx not in self._flat:
+            p, n = ctypes.c_void_p(), ctypes.c_int64()
+            check(lib().p3d_vae_flat_ptr(self._h, idx, ctypes.byref(p), ctypes.byref(n)), "p3d_vae_flat_ptr")
+            self._flat[idx] = _p3d.device_view(p.value, (n.value,), self.device.index)
+        return self._flat[idx]
+
+    def _tensors(self, which):
+        f = self.flat(which)
+        return {n: f[o:o + int(np.prod(s))].view(*s) for n, s, o in self.param_table}
+
+    def variable(self, name):
+        return self._tensors("params")[name]
+
+    def grads(self):
+        """{keras name: gradient} as numpy arrays (after compute_gradients / a training step)."""
+        return {n: t.cpu().numpy() for n, t in self._tensors("grads").items()}
+
+    def slots(self):
+        """({name: adam m}, {name: adam v}) as numpy arrays."""
+        return ({n: t.cpu().numpy() for n, t in self._tensors("adam_m").items()},
+                {n: t.cpu().numpy() for n, t in self._tensors("adam_v").items()})
+
+    def initialize(self, seed=0):
+        """Glorot-uniform kernels, zero biases (keras.layers.Dense defaults, models.py:29-49)."""
+        rng = np.random.default_rng(seed)
+        w = []
+        for name, shape, _ in self.param_table:
+            if name.endswith("/kernel"):
+                lim = np.sqrt(6.0 / (shape[0] + shape[1]))
+                w.append(rng.uniform(-lim, lim, shape).astype(np.float32))
+            else:
+                w.append(np.zeros(shape, np.float32))
+        self.set_weights(w)
+
+    def get_weights(self):
+        return [t.cpu().numpy() for t in self._tensors("params").values()]
+
+    def set_weights(self, weights):
+        if isinstance(weights, dict):
+            weights = [weights[n] for n, _, _ in self.param_table]
+        if len(weights) != len(self.param_table):
+            raise ValueError("set_weights: expected %d arrays, got %d" % (len(self.param_table), len(weights)))
+        views = self._tensors("params")
+        for (name, shape, _), w in zip(self.param_table, weights):
+            w = np.array(w, dtype=np.float32)      # (a writable copy: torch.from_numpy below)
+            if tuple(w.shape) != tuple(shape):
+                raise ValueError("set_weights: %s expects shape %s, got %s" % (name, shape, w.shape))
+            views[name].copy_(self.torch.from_numpy(np.ascontiguousarray(w)))
+        check(lib().p3d_vae_params_updated(self._h, self.stream()), "p3d_vae_params_updated")
+
+    def save_weights(self, path):
+        np.savez(path if str(path).endswith(".npz") else str(path) + ".npz",
+                 **{n: w for (n, _, _), w in zip(self.param_table, self.get_weights())})
+
+    def load_weights(self, path):
+        with np.load(path if str(path).endswith(".npz") else str(path) + ".npz", allow_pickle=False) as z:
+            self.set_weights({n: z[n] for n, _, _ in self.param_table})
+
+    def get_step(self):
+        s, b1, b2 = ctypes.c_int64(), ctypes.c_float(), ctypes.c_float()
+        check(lib().p3d_vae_get_step(self._h, ctypes.byref(s), ctypes.byref(b1), ctypes.byref(b2)), "p3d_vae_get_step")
+        return s.value, b1.value, b2.value
+
+    def set_step(self, step, b1p=None, b2p=None):
+        b1p = np.float32(0.9) ** (step + 1) if b1p is None else b1p
+        b2p = np.float32(0.999) ** (step + 1) if b2p is None else b2p
+        check(lib().p3d_vae_set_step(self._h, int(step), float(b1p), float(b2p)), "p3d_vae_set_step")
+
+    def set_form(self, form):
+        check(lib().p3d_vae_set_form(self._h, int(form)), "p3d_vae_set_form")
+
+    def _dev(self, a, width, what):
+        torch = self.torch
+        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.array(a, dtype=np.float32, order="C"))
+        if t.dim() != 2 or t.shape[1] != width:
+            raise ValueError("%s: expected shape [None, %d], got %s" % (what, width, tuple(t.shape)))
+        if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
+            t = t.to(device=self.device, dtype=torch.float32).contiguous()
+        return t
+
+    def _factors(self, factors):
+        return (ctypes.c_float * 3)(*[float(f) for f in factors])
+
+    # ------------------------------------------------------------------ device entry points
+    def forward_device(self, x, eps=None, ctr=0, target=None, want=("y",)):
+        """One k_vae_fwd launch; returns a dict with the tensors named in `want` out of 'y',
+        'mean', 'log_var', 'z' and, with a target, 'row_terms' [B, 3]."""
+        torch = self.torch
+        x = self._dev(x, self.input_size, "vae input")
+        B = x.shape[0]
+        eps = None if eps is None else self._dev(eps, self.latent_dim, "eps")
+        if eps is not None and eps.shape[0] != B:
+            raise ValueError("eps: expected %d rows, got %d" % (B, eps.shape[0]))
+        target = None if target is None else self._dev(target, self.human_3d_size, "target")
+        if target is not None and target.shape[0] != B:
+            raise ValueError("target: expected %d rows, got %d" % (B, target.shape[0]))
+        widths = {"y": self.human_3d_size, "mean": self.latent_dim, "log_var": self.latent_dim, "z": self.latent_dim}
+        out = {k: torch.empty((B, widths[k]), dtype=torch.float32, device=self.device) for k in want if k in widths}
+        if target is not None:
+            out["row_terms"] = torch.empty((B, 3), dtype=torch.float32, device=self.device)
+        check(lib().p3d_vae_forward(self._h, ptr(x), B, ptr(eps), int(ctr), ptr(out.get("y")), ptr(out.get("mean")),
+                                    ptr(out.get("log_var")), ptr(out.get("z")), ptr(target), ptr(out.get("row_terms")),
+                                    self.stream()), "p3d_vae_forward")
+        return out
+
+    def _step(self, fn, what, x, t, eps, middle, loss_out=None):
+        """`middle`: the arguments between eps and loss3_dev (ctr, factors | factors, lr)."""
+        x = self._dev(x, self.input_size, "vae input")
+        t = self._dev(t, self.human_3d_size, "target")
+        if t.shape[0] != x.shape[0]:
+            raise ValueError("target: expected %d rows, got %d" % (x.shape[0], t.shape[0]))
+        eps = None if eps is None else self._dev(eps, self.latent_dim, "eps")
+        if eps is not None and eps.shape[0] != x.shape[0]:
+            raise ValueError("eps: expected %d rows, got %d" % (x.shape[0], eps.shape[0]))
+        loss = self._loss if loss_out is None else loss_out
+        check(fn(self._h, ptr(x), ptr(t), x.shape[0], ptr(eps), *middle, ptr(loss), self.stream()), what)
+        return loss
+
+    def loss_device(self, x, t, factors, eps=None, ctr=0, loss_out=None):
+        """ELBO.compute_loss: the device 3-vector [like, kcs, dkl]."""
+        return self._step(lib().p3d_vae_loss, "p3d_vae_loss", x, t, eps, (int(ctr), self._factors(factors)), loss_out)
+
+    def compute_gradients(self, x, t, factors, eps=None, ctr=0, loss_out=None):
+        """Loss and tape.gradient of the three terms' sum into the gradient buffer (no optimizer)."""
+        return self._step(lib().p3d_vae_grad, "p3d_vae_grad", x, t, eps, (int(ctr), self._factors(factors)), loss_out)
+
+    def train_step_device(self, x, t, factors, lr, eps=None, loss_out=None):
+        """Loss, gradient and Keras Adam; one launch at B <= 64.  Capturable."""
+        return self._step(lib().p3d_vae_train_step, "p3d_vae_train_step", x, t, eps,
+                          (self._factors(factors), float(lr)), loss_out)
+
+    def adam_apply(self, lr):
+        check(lib().p3d_vae_adam_apply(self._h, float(lr), self.stream()), "p3d_vae_adam_apply")
+
+    def eps_device(self, B, ctr=0, row0=0):
+        out = self.torch.empty((B, self.latent_dim), dtype=self.torch.float32, device=self.device)
+        check(lib().p3d_vae_eps(self.seed, int(ctr), int(row0), B, self.latent_dim, ptr(out), self.stream()),
+              "p3d_vae_eps")
+        return out
+
+    # ------------------------------------------------------------------ the reference's interface
+    def encode(self, x):
+        """mean and log variance of Q(z|x) (models.py:62-65)."""
+        o = self.forward_device(x, eps=self.torch.zeros((len(x), self.latent_dim), device=self.device),
+                                want=("mean", "log_var"))
+        return o["mean"], o["log_var"]
+
+    def reparametrize(self, mean, log_var):
+        """eps exp(0.5 log_var) + mean with eps from the library's stream (models.py:68-71)."""
+        self._calls += 1
+        eps = self.eps_device(mean.shape[0], ctr=self._calls)
+        return eps * self.torch.exp(log_var * 0.5) + mean
+
+    def decode(self, z):
+        """models.py:74-76 -- the decoder alone is not a library entry point."""
+        raise NotImplementedError("VAE.decode on its own is not built: the filter runs encode, reparametrize and "
+                                  "decode in one launch (call the model, or forward_device for z and y together)")
+
+    def __call__(self, inputs, training=False, eps=None):
+        self._calls += 1
+        return self.forward_device(inputs, eps=eps, ctr=self._calls)["y"]
+
+    def get_config(self):
+        return {"input_size": self.input_size, "latent_dim": self.latent_dim, "enc_dim": self.enc_dim,
+                "dec_dim": self.dec_dim, "human_3d_size": self.human_3d_size}
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            self._flat.clear()
+            lib().p3d_vae_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Pose3DVae(object):
+    """The frozen lifter + the VAE filter (models.py:485-540): call(x2d) -> (out_3d, out_vae), both
+    on the device with no host round trip between p3d_serve and p3d_vae_forward."""
+
+    def __init__(self, latent_dim, enc_dim, dec_dim, use_effnet_ouptut=False, use_2d=False, pred_bones=False, *,
+                 pose3d=None, max_batch=4096, seed=None):
+        if use_2d:
+            raise NotImplementedError("Pose3DVae(use_2d=True) (the 80-input filter over [x2d, out_3d]) is not built")
+        if use_effnet_ouptut:
+            raise NotImplementedError("Pose3DVae(use_effnet_ouptut=True) (EfficientNet features) is not built")
+        if pred_bones:
+            raise NotImplementedError("Pose3DVae(pred_bones=True) (VAEBones) is not built")
+        if pose3d is None:
+            raise ValueError("Pose3DVae needs the lifter: pass pose3d=LinearModel(...) (the reference builds its "
+                             "PoseBase here; this package's lifter is linear_model.LinearModel)")
+        self.use_2d, self.use_effnet_ouptut, self.pred_bones = False, False, False
+        self.human_3d_size, self.human_2d_size = HUMAN_3D_SIZE, HUMAN_2D_SIZE
+        if pose3d.output_size != HUMAN_3D_SIZE:
+            raise ValueError("Pose3DVae: the lifter must predict %d outputs, not %d" % (HUMAN_3D_SIZE, pose3d.output_size))
+        self.pose3d = pose3d
+        self.vae = VAE(HUMAN_3D_SIZE, latent_dim, enc_dim, dec_dim, max_batch=max_batch, seed=seed,
+                       device=pose3d.device.index)
+
+    def __call__(self, inputs, effnet_output=None, training=False, eps=None):
+        if effnet_output is not None:
+            raise NotImplementedError("Pose3DVae: effnet_output is not built")
+        out_3d = self.pose3d.serve_device(inputs)      # raises ValueError on a bad shape
+        return out_3d, self.vae(out_3d, training=training, eps=eps)
+
+    def save_weights(self, path):
+        self.vae.save_weights(path)
+
+    def load_weights(self, path):
+        self.vae.load_weights(path)
+
+    def close(self):
+        self.vae.close()

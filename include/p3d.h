@@ -490,6 +490,87 @@ int p3d_moments(const double* x, int64_t F, int32_t D, double* mean, double* std
  * buffer; pass a previous result to continue it.  Host only, no device work. */
 uint32_t p3d_crc32c(const void* data, int64_t n, uint32_t crc);
 
+/* ------------------------------------------------------------------------------------------
+ * The VAE pose filter on top of the frozen lifter: src/top_vae_3d_pose/models.py:12-91 (VAE),
+ * src/top_vae_3d_pose/losses.py:12-109 (ELBO) and src/3d_pose_vae_filter.py:188-196
+ * (train_step_vae).  A dense net in -> enc_dims (ReLU) -> {mean, log_varianze} [latent] ->
+ * z = eps exp(0.5 log_var) + mean -> dec_dims (ReLU) -> out, whose whole parameter set lives in
+ * one workgroup's LDS (csrc/p3d_vae.h).  All pointers are device pointers (`factors`: three host
+ * floats, read at the call), every call is asynchronous on `stream` and capturable; argument
+ * errors answer without a GPU.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct p3d_vae p3d_vae;
+
+/* keras.Model construction of models.py:25-52.  in <= 256; 1-4 hidden layers each side, widths
+ * <= 256; latent <= 64; out <= 64; every width a multiple of 8; max_batch <= 2^20 bounds the
+ * rows of the loss / gradient / training calls; the parameters and the working space of four
+ * 16-row tiles must fit one workgroup's LDS.  Anything else: P3D_ERR_ARG and a message.
+ * Parameters start at zero (the host writes Glorot kernels through the parameter table);
+ * `seed` keys the eps stream. */
+int p3d_vae_create(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent, int32_t n_dec,
+                   const int32_t* dec_dims, int32_t out, int32_t max_batch, uint64_t seed, p3d_vae** v);
+int p3d_vae_destroy(p3d_vae* v);
+/* Bytes of LDS a workgroup of this shape's kernels uses (the packed parameters + four 16-row
+ * tiles of activations), as p3d_vae_create lays them out; 0 for a shape it refuses for another
+ * reason.  Host only. */
+int64_t p3d_vae_lds_bytes(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent, int32_t n_dec,
+                          const int32_t* dec_dims, int32_t out);
+
+/* Parameter table in Keras order and names (model.get_weights(), models.py:29-49):
+ * "enc_h_<units>/kernel", "enc_h_<units>/bias", ..., "mean/kernel", "mean/bias",
+ * "log_varianze/kernel", "log_varianze/bias", "dec_f_<units>/kernel", ..., "dec_f_out/bias".
+ * Kernels are [rows = in, cols = out] row-major masters, biases [1, cols]; `offset` is the
+ * tensor's place in the flat buffers. */
+int p3d_vae_param_count(const p3d_vae* v, int32_t* count);
+int p3d_vae_param_info(const p3d_vae* v, int32_t idx, const char** name, int64_t* numel, int32_t* rows,
+                       int32_t* cols, int64_t* offset);
+int p3d_vae_param_ptr(p3d_vae* v, const char* name, void** dptr, int64_t* numel);
+/* Flat device buffers sharing the parameter table's layout (0 params, 1 grads, 2 adam_m,
+ * 3 adam_v), and 4: the workspace of per-block partial gradients, 5: the packed copy. */
+int p3d_vae_flat_ptr(p3d_vae* v, int32_t which, void** dptr, int64_t* numel);
+/* Re-derive the packed copy after the host wrote parameters (model.set_weights). */
+int p3d_vae_params_updated(p3d_vae* v, void* stream);
+
+/* VAE.call (models.py:62-80): y [B, out] from x [B, in], any B up to 2^20.  eps [B, latent] is
+ * the caller's, or (null) drawn from the library's Philox stream keyed (seed, ctr, row, column)
+ * -- tf.random.normal's own stream is not reproducible.  mean, log_var, z [B, latent] are
+ * written when non-null; with a target [B, out], row_terms [B, 3] receives per row the mean
+ * square likelihood, the KCS error (out == 48 only, else 0) and the KL divergence of
+ * losses.py:29-32.  ctr = P3D_CTR_GLOBAL_STEP reads the device step counter. */
+int p3d_vae_forward(p3d_vae* v, const float* x, int64_t B, const float* eps, uint64_t ctr, float* y, float* mean,
+                    float* log_var, float* z, const float* target, float* row_terms, void* stream);
+
+/* ELBO.compute_loss (losses.py:14-40): loss3_dev = [likef mean_B like, kcsf mean_B kcs,
+ * dklf mean_B dkl] for factors = {likef, kcsf, dklf}; B <= max_batch.  kcsf must be 0 unless
+ * out == 48 (P3D_ERR_ARG). */
+int p3d_vae_loss(p3d_vae* v, const float* x, const float* t, int64_t B, const float* eps, uint64_t ctr,
+                 const float* factors, float* loss3_dev, void* stream);
+/* The same plus tape.gradient of the three terms' sum (3d_pose_vae_filter.py:191-194) into the
+ * gradient buffer; no optimizer.  Sums are associated by row index alone (16-row tiles in order
+ * inside a 64-row block, blocks in order), so the gradient does not depend on the launch form. */
+int p3d_vae_grad(p3d_vae* v, const float* x, const float* t, int64_t B, const float* eps, uint64_t ctr,
+                 const float* factors, float* loss3_dev, void* stream);
+/* train_step_vae (3d_pose_vae_filter.py:188-196): loss, gradient and Keras Adam
+ * (optimizer.apply_gradients; beta 0.9 / 0.999, epsilon 1e-7) with the device step counter as
+ * the eps counter.  B <= 64 is ONE launch; larger batches add the block reduction + Adam launch. */
+int p3d_vae_train_step(p3d_vae* v, const float* x, const float* t, int64_t B, const float* eps,
+                       const float* factors, float lr, float* loss3_dev, void* stream);
+/* Keras Adam over the gradient buffer as it stands (after p3d_vae_grad): the stand-alone form
+ * of the optimizer inside p3d_vae_train_step, bit-identical to it. */
+int p3d_vae_adam_apply(p3d_vae* v, float lr, void* stream);
+/* form = 1 runs p3d_vae_grad / p3d_vae_train_step through the per-block partials and the
+ * reduction launch also at B <= 64 (0, the default: one launch there).  Same bits either way. */
+int p3d_vae_set_form(p3d_vae* v, int32_t form);
+/* optimizer.iterations and the beta powers (device-resident; these two calls synchronise). */
+int p3d_vae_get_step(const p3d_vae* v, int64_t* step, float* beta1_power, float* beta2_power);
+int p3d_vae_set_step(p3d_vae* v, int64_t step, float beta1_power, float beta2_power);
+
+/* Rows row0 .. row0 + B - 1 of the eps stream (tf.random.normal of models.py:70) as
+ * p3d_vae_forward draws them: out [B, latent], latent a multiple of 4. */
+int p3d_vae_eps(uint64_t seed, uint64_t ctr, int64_t row0, int64_t B, int32_t latent, float* out, void* stream);
+/* Bytes of the library-owned workspace a gradient over B rows uses (per-block partials). */
+int64_t p3d_vae_workspace(const p3d_vae* v, int64_t B);
+
 #ifdef __cplusplus
 }
 #endif
