@@ -145,6 +145,11 @@ SIGNATURES = [
     ("p3d_vae_set_step", c_int32, [c_void_p, c_int64, c_float, c_float]),
     ("p3d_vae_eps", c_int32, [c_uint64, c_uint64, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
     ("p3d_vae_workspace", c_int64, [c_void_p, c_int64]),
+    ("p3d_vae_seq_filter", c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_uint64, c_int64,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("p3d_vae_seq_set_form", c_int32, [c_void_p, c_int32]),
+    ("p3d_vae_seq_lds_bytes", c_int64, [c_int32, c_int32, POINTER(c_int32), c_int32, c_int32, POINTER(c_int32),
+                                        c_int32, c_int32]),
 ]
 
 

@@ -40,6 +40,7 @@
 
 #include "p3d_layers.h"
 #include "p3d_vae.h"
+#include "p3d_vae_seq.h"
 
 // =====================================================================================
 // host side
@@ -2614,6 +2615,10 @@ struct p3d_vae {
   float* pk = nullptr; float* ws = nullptr;
   int* pkidx = nullptr;                 // flat element -> packed copy (device)
   VaeState* st = nullptr;
+  // the sequence filter (k_vae_seq / k_vae_seq4): 0 seq_lds = this shape has none; form 1 is the
+  // default by measurement (MEASUREMENTS.md §14: 5.5 against 14.6 us per frame step at H3.6M size)
+  int seq_form = 1, seq_len = 0, seq_xoff = 0, seq_toff = 0, seq_ldt = 0, seq_moff = 0;
+  size_t seq_lds = 0;
 };
 
 namespace {
@@ -2698,6 +2703,19 @@ size_t vae_best_layout(VaeDesc& d, std::vector<std::string>& names, int in, int 
     if (lds <= P3D_VAE_LDS_LIMIT) break;
   }
   return lds;
+}
+
+// The sequence filter's LDS behind the packed copy (float offsets): ONE tile's activation area, the
+// [16, in] state tile (the area's own input tile where the layout stages one), the frame's target
+// tile and the 16 rows' first frame (int64) and frame count (int).  Returns the dynamic LDS bytes.
+size_t vae_seq_layout(const VaeDesc& d, int& xoff, int& toff, int& ldt, int& moff) {
+  int act = d.act;
+  xoff = d.xbuf;
+  if (xoff < 0) { xoff = act; act += (16 * d.ldx + 3) / 4 * 4; }
+  ldt = ceil16(d.out) + 2;
+  toff = act; act += 16 * ldt;
+  moff = act; act += 16 * 2 + 16;   // (act stays a multiple of 4: the int64 offsets are aligned)
+  return sizeof(float) * ((size_t)d.Ppk + (size_t)act);
 }
 
 int vae_check_call(const p3d_vae* v, const float* x, int64_t B, const char* what) {
@@ -2843,6 +2861,17 @@ extern "C" int p3d_vae_create(int32_t in, int32_t n_enc, const int32_t* enc_dims
     return bail(e, "hipFuncSetAttribute(k_vae_fwd)");
   if ((e = hipFuncSetAttribute((const void*)k_vae_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->lds)) != hipSuccess)
     return bail(e, "hipFuncSetAttribute(k_vae_step)");
+  if (in % out == 0 && in / out <= P3D_VAE_SEQ_MAX_LEN) {
+    const size_t sl = vae_seq_layout(v->desc, v->seq_xoff, v->seq_toff, v->seq_ldt, v->seq_moff);
+    if (sl <= P3D_VAE_LDS_LIMIT) {
+      v->seq_len = in / out;
+      v->seq_lds = sl;
+      if ((e = hipFuncSetAttribute((const void*)k_vae_seq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sl)) != hipSuccess)
+        return bail(e, "hipFuncSetAttribute(k_vae_seq)");
+      if ((e = hipFuncSetAttribute((const void*)k_vae_seq4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sl)) != hipSuccess)
+        return bail(e, "hipFuncSetAttribute(k_vae_seq4)");
+    }
+  }
   *vout = v;
   return P3D_OK;
 }
@@ -2977,6 +3006,56 @@ extern "C" int p3d_vae_eps(uint64_t seed, uint64_t ctr, int64_t row0, int64_t B,
   hipLaunchKernelGGL(k_vae_eps, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seed, ctr,
                      row0, B, (int)latent, out);
   LAUNCH_CHECK("k_vae_eps");
+  return P3D_OK;
+}
+
+extern "C" int64_t p3d_vae_seq_lds_bytes(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent,
+                                         int32_t n_dec, const int32_t* dec_dims, int32_t out, int32_t form) {
+  if (form != 0 && form != 1) return 0;
+  if (vae_check_shape(in, n_enc, enc_dims, latent, n_dec, dec_dims, out)) return 0;
+  if (in % out != 0 || in / out > P3D_VAE_SEQ_MAX_LEN) return 0;
+  VaeDesc d;
+  std::vector<std::string> names;
+  if (vae_best_layout(d, names, in, n_enc, enc_dims, latent, n_dec, dec_dims, out) > P3D_VAE_LDS_LIMIT) return 0;
+  int xoff, toff, ldt, moff;
+  return (int64_t)vae_seq_layout(d, xoff, toff, ldt, moff);   // (both forms run one tile per workgroup)
+}
+
+extern "C" int p3d_vae_seq_set_form(p3d_vae* v, int32_t form) {
+  if (!v || (form != 0 && form != 1)) return fail(P3D_ERR_ARG, "p3d_vae_seq_set_form: form must be 0 or 1");
+  v->seq_form = form;
+  return P3D_OK;
+}
+
+extern "C" int p3d_vae_seq_filter(p3d_vae* v, const float* pred, const int64_t* seq_off, int64_t S, int64_t N,
+                                  const float* eps, uint64_t ctr, int64_t eps_row0, const float* target,
+                                  float* state, int32_t* started, float* ref, float* frame_err, double* seq_err,
+                                  void* stream) {
+  if (!v || !pred || !seq_off || !ref) return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: null argument");
+  if (v->desc.in % v->desc.out != 0 || v->desc.in / v->desc.out > P3D_VAE_SEQ_MAX_LEN)
+    return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: in must be seq_len * out with seq_len in 1 .. " +
+                                 std::to_string(P3D_VAE_SEQ_MAX_LEN));
+  if (!v->seq_lds)
+    return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: parameters, one tile and the state tile exceed a workgroup's LDS");
+  if (S < 1 || S > (1 << 20)) return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: S must be in 1 .. 2^20");
+  if (N < 1 || N > (1 << 20)) return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: N must be in 1 .. 2^20");
+  if (eps_row0 < 0) return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: eps_row0 must be >= 0");
+  if ((state != nullptr) != (started != nullptr))
+    return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: state and started go together");
+  if ((frame_err || seq_err) && !target)
+    return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: frame_err and seq_err need a target");
+  for (const void* p : {(const void*)pred, (const void*)eps, (const void*)target, (const void*)state, (const void*)ref})
+    if ((uintptr_t)p % 16 != 0)
+      return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: pred, eps, target, state and ref must be 16-byte aligned");
+  VaeSeqArgs a{};
+  a.desc = v->desc; a.desc_dev = v->d_desc; a.pk = v->pk; a.pred = pred; a.seq_off = seq_off; a.S = S; a.N = N;
+  a.eps = eps; a.seed = v->seed; a.ctr = ctr; a.eps_row0 = eps_row0; a.target = target;
+  a.state = state; a.started = started; a.ref = ref; a.frame_err = frame_err; a.seq_err = seq_err;
+  a.seq_len = v->seq_len; a.xoff = v->seq_xoff; a.toff = v->seq_toff; a.ldt = v->seq_ldt; a.moff = v->seq_moff;
+  const unsigned grid = (unsigned)((S + 15) / 16);
+  if (v->seq_form == 0) hipLaunchKernelGGL(k_vae_seq, dim3(grid), dim3(64), v->seq_lds, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(k_vae_seq4, dim3(grid), dim3(256), v->seq_lds, (hipStream_t)stream, a);
+  LAUNCH_CHECK("k_vae_seq");
   return P3D_OK;
 }
 

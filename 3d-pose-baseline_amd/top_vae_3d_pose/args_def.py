@@ -39,6 +39,12 @@ def build_parser():
     p.add_argument("--sample", action='store_true', default=False, help="Set to True for sampling.")
     p.add_argument("--load", type=int, default=0, help="Try to load a previous checkpoint.")
     p.add_argument("--verbose", type=int, default=2, help="0:Error, 1:Warning, 2:INFO*(default), 3:debug")
+    p.add_argument("--noise_3d", type=float, nargs=2, default=[1, 1],
+                   help="Noise added for 3d points, second value is a noise added over a single joint")
+    p.add_argument("--evaluate", action='store_true', default=False, help="Set to True for evaluating.")
+    # build-specific: where evaluate() of 3d_pose_vae_filter_kin.py reads the filter's weights
+    p.add_argument("--vae_weights", type=str, default=None,
+                   help="The .npz of VAE weights that --evaluate loads (default: the one train() saves)")
     # build-specific: the frozen lifter (the reference hard-codes PoseBase and its checkpoint path)
     p.add_argument("--linear_size", type=int, default=1024, help="Lifter: size of each model layer")
     p.add_argument("--num_layers", type=int, default=2, help="Lifter: number of two_linear blocks")

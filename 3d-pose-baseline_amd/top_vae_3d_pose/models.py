@@ -216,6 +216,97 @@ class VAE(object):
               "p3d_vae_eps")
         return out
 
+    # ------------------------------------------------------------------ the recurrence over sequences
+    def _seq_len(self):
+        if self.input_size % self.human_3d_size != 0 or not 1 <= self.input_size // self.human_3d_size <= 5:
+            raise ValueError("filter_sequences: input_size %d is not 1 .. 5 times human_3d_size %d"
+                             % (self.input_size, self.human_3d_size))
+        return self.input_size // self.human_3d_size
+
+    SEQ_FORM_DEFAULT = 1   # the library's default, by measurement (MEASUREMENTS.md)
+
+    def set_seq_form(self, form):
+        """0: one wave per 16-sequence tile; 1 (the default): four waves per tile.  Same bits either way."""
+        check(lib().p3d_vae_seq_set_form(self._h, int(form)), "p3d_vae_seq_set_form")
+
+    def new_seq_state(self, S):
+        """The zeroed (state [S, (seq_len - 1) * out], started [S]) pair that carries filter_sequences'
+        buffer from one chunk of a stream to the next."""
+        torch = self.torch
+        w = (self._seq_len() - 1) * self.human_3d_size
+        return (torch.zeros((int(S), w), dtype=torch.float32, device=self.device),
+                torch.zeros((int(S),), dtype=torch.int32, device=self.device))
+
+    def filter_sequences(self, pred, seq_off, eps=None, ctr=None, eps_row0=0, target=None, state=None,
+                         want=("ref",)):
+        """The temporal filter run as the reference's evaluate() recurrence over whole sequences in
+        one k_vae_seq launch: frame f's refined pose feeds the windows of the next seq_len - 1.
+
+        pred [N, out] holds the lifter's outputs with the sequences concatenated, seq_off [S + 1]
+        their first frames (seq_off[0] = 0, seq_off[S] = N; empty sequences are legal).  A host
+        seq_off (list, numpy, CPU tensor) is checked and uploaded; a device tensor is taken as it is,
+        without a host round trip (the kernel clamps it into [0, N]), so the call stays capturable.
+        eps [N, latent], or None for the library's Philox stream at (ctr, eps_row0 + frame index);
+        ctr=None draws a fresh counter.  state is a new_seq_state() pair, updated in place.
+        Returns a dict with the entries of `want` out of 'ref' [N, out], 'frame_err' [N, 2]
+        {err_pred, err_ref} and 'seq_err' [S, 2] (float64); the last two need a target."""
+        torch = self.torch
+        self._seq_len()
+        pred = self._dev(pred, self.human_3d_size, "pred")
+        N = pred.shape[0]
+        if isinstance(seq_off, torch.Tensor) and seq_off.is_cuda:
+            off = seq_off
+            if off.dim() != 1 or off.dtype != torch.int64 or off.shape[0] < 2 or not off.is_contiguous():
+                raise ValueError("seq_off: expected a contiguous int64 vector [S + 1], got %s %s"
+                                 % (off.dtype, tuple(off.shape)))
+            if off.device != self.device:
+                off = off.to(self.device)
+        else:
+            h = np.asarray(seq_off.numpy() if isinstance(seq_off, torch.Tensor) else seq_off)
+            if h.ndim != 1 or h.shape[0] < 2 or not np.issubdtype(h.dtype, np.integer):
+                raise ValueError("seq_off: expected an integer vector [S + 1], got %s %s" % (h.dtype, h.shape))
+            h = h.astype(np.int64)
+            if h[0] != 0 or h[-1] != N or (np.diff(h) < 0).any():
+                raise ValueError("seq_off: offsets must start at 0, not decrease and end at N = %d (got %d .. %d)"
+                                 % (N, h[0], h[-1]))
+            off = torch.from_numpy(h).to(self.device)
+        S = off.shape[0] - 1
+        eps = None if eps is None else self._dev(eps, self.latent_dim, "eps")
+        if eps is not None and eps.shape[0] != N:
+            raise ValueError("eps: expected %d rows, got %d" % (N, eps.shape[0]))
+        target = None if target is None else self._dev(target, self.human_3d_size, "target")
+        if target is not None and target.shape[0] != N:
+            raise ValueError("target: expected %d rows, got %d" % (N, target.shape[0]))
+        unknown = [k for k in want if k not in ("ref", "frame_err", "seq_err")]
+        if unknown:
+            raise ValueError("filter_sequences: unknown outputs %s" % unknown)
+        if target is None and ("frame_err" in want or "seq_err" in want):
+            raise ValueError("filter_sequences: frame_err and seq_err need a target")
+        st, started = (None, None) if state is None else state
+        if state is not None:
+            w = (self._seq_len() - 1) * self.human_3d_size
+            if (tuple(st.shape) != (S, w) or tuple(started.shape) != (S,) or st.dtype != torch.float32
+                    or started.dtype != torch.int32 or st.device != self.device or started.device != self.device
+                    or not st.is_contiguous() or not started.is_contiguous()):
+                raise ValueError("state: expected the (float32 [%d, %d], int32 [%d]) pair of new_seq_state" % (S, w, S))
+        if ctr is None:
+            self._calls += 1
+            ctr = self._calls
+        out = {"ref": torch.empty((N, self.human_3d_size), dtype=torch.float32, device=self.device)}
+        if "frame_err" in want:
+            out["frame_err"] = torch.empty((N, 2), dtype=torch.float32, device=self.device)
+        if "seq_err" in want:
+            out["seq_err"] = torch.empty((S, 2), dtype=torch.float64, device=self.device)
+        if N == 0:
+            if "seq_err" in out:
+                out["seq_err"].zero_()
+        else:
+            check(lib().p3d_vae_seq_filter(self._h, ptr(pred), ptr(off), S, N, ptr(eps), int(ctr), int(eps_row0),
+                                           ptr(target), ptr(st), ptr(started), ptr(out["ref"]),
+                                           ptr(out.get("frame_err")), ptr(out.get("seq_err")), self.stream()),
+                  "p3d_vae_seq_filter")
+        return {k: out[k] for k in want}
+
     # ------------------------------------------------------------------ the reference's interface
     def encode(self, x):
         """mean and log variance of Q(z|x) (models.py:62-65)."""

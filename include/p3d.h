@@ -571,6 +571,38 @@ int p3d_vae_eps(uint64_t seed, uint64_t ctr, int64_t row0, int64_t B, int32_t la
 /* Bytes of the library-owned workspace a gradient over B rows uses (per-block partials). */
 int64_t p3d_vae_workspace(const p3d_vae* v, int64_t B);
 
+/* The temporal filter (in == seq_len * out, 1 <= seq_len <= 5) run as the reference's recurrence
+ * (3d_pose_vae_filter_kin.py evaluate()) over S whole sequences in ONE launch:
+ *
+ *   buffer = [p_0] * seq_len
+ *   per frame f: buffer = buffer[1:] + [p_f];  r_f = VAE(concat(buffer), eps_f);  buffer[-1] = r_f
+ *
+ * Row r of frame f is bit-identical to p3d_vae_forward on the same input and eps row.  eps null:
+ * the Philox stream p3d_vae_eps(seed, ctr, eps_row0, N, ...) gives.  err_pred / err_ref are
+ * mean_out (target - p_f)^2 and mean_out (target - r_f)^2 per frame (float32) and their
+ * frame-ordered sums per sequence (double).  state / started carry the buffer's first seq_len - 1
+ * groups across calls so that a stream can be filtered in chunks: started[s] == 0 primes the
+ * buffer from the chunk's first frame and sets started[s] = 1.  Empty sequences write nothing
+ * (their seq_err is 0) and leave their state untouched.  Asynchronous, capturable; all pointers
+ * are device pointers, the float arrays 16-byte aligned.  S and N in 1 .. 2^20. */
+int p3d_vae_seq_filter(p3d_vae* v,
+        const float* pred,          /* [N, out] lifter outputs, sequences concatenated          */
+        const int64_t* seq_off,     /* device, [S + 1], non-decreasing, seq_off[0] = 0, [S] = N */
+        int64_t S, int64_t N,
+        const float* eps, uint64_t ctr, int64_t eps_row0,
+        const float* target,        /* [N, out] or null                                          */
+        float* state, int32_t* started,  /* [S, (seq_len-1) * out], [S]; both null = fresh, stateless */
+        float* ref,                 /* [N, out]                                                  */
+        float* frame_err,           /* [N, 2] {err_pred, err_ref} or null (needs target)         */
+        double* seq_err,            /* [S, 2] frame-ordered sums of the above, or null           */
+        void* stream);
+/* form 0: one wave per 16-sequence tile; form 1 (the default, the faster one as measured): four
+ * waves per tile, a layer's column tiles dealt among them.  Same bits either way. */
+int p3d_vae_seq_set_form(p3d_vae* v, int32_t form);
+/* Dynamic LDS bytes of the sequence kernel for a shape; 0 for a shape it does not serve.  Host only. */
+int64_t p3d_vae_seq_lds_bytes(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent,
+                              int32_t n_dec, const int32_t* dec_dims, int32_t out, int32_t form);
+
 #ifdef __cplusplus
 }
 #endif
