@@ -28,6 +28,12 @@ class P3DCfg(ctypes.Structure):
                 ("bn_eps", c_float), ("bn_momentum", c_float)]
 
 
+class P3DVaeCat(ctypes.Structure):
+    """p3d_vae_cat (include/p3d.h): the VAE filter's input as up to four column segments."""
+    _fields_ = [("n", c_int32), ("p", c_void_p * 4), ("w", c_int32 * 4), ("idx", c_void_p * 4),
+                ("rows", c_int64 * 4)]
+
+
 class P3DError(RuntimeError):
     pass
 
@@ -145,6 +151,15 @@ SIGNATURES = [
     ("p3d_vae_set_step", c_int32, [c_void_p, c_int64, c_float, c_float]),
     ("p3d_vae_eps", c_int32, [c_uint64, c_uint64, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
     ("p3d_vae_workspace", c_int64, [c_void_p, c_int64]),
+    ("p3d_vae_cat_check", c_int32, [POINTER(P3DVaeCat), c_int32, c_int64]),
+    ("p3d_vae_forward_cat", c_int32, [c_void_p, POINTER(P3DVaeCat), c_int64, c_void_p, c_uint64, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("p3d_vae_loss_cat", c_int32, [c_void_p, POINTER(P3DVaeCat), c_void_p, c_int64, c_void_p, c_uint64,
+                                   POINTER(c_float), c_void_p, c_void_p]),
+    ("p3d_vae_grad_cat", c_int32, [c_void_p, POINTER(P3DVaeCat), c_void_p, c_int64, c_void_p, c_uint64,
+                                   POINTER(c_float), c_void_p, c_void_p]),
+    ("p3d_vae_train_step_cat", c_int32, [c_void_p, POINTER(P3DVaeCat), c_void_p, c_int64, c_void_p, POINTER(c_float),
+                                         c_float, c_void_p, c_void_p]),
     ("p3d_vae_seq_filter", c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_uint64, c_int64,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("p3d_vae_seq_set_form", c_int32, [c_void_p, c_int32]),
@@ -227,5 +242,5 @@ def stream_handle(stream=None) -> int:
     return int(stream.cuda_stream)
 
 
-__all__ = ["P3DCfg", "P3DError", "lib", "check", "device_view", "ptr", "stream_handle",
+__all__ = ["P3DCfg", "P3DVaeCat", "P3DError", "lib", "check", "device_view", "ptr", "stream_handle",
            "LIB_PATH", "SIGNATURES", "c_double"]

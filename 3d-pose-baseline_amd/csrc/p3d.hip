@@ -41,6 +41,7 @@
 #include "p3d_layers.h"
 #include "p3d_vae.h"
 #include "p3d_vae_seq.h"
+#include "p3d_vae_wide.h"
 
 // =====================================================================================
 // host side
@@ -2619,6 +2620,12 @@ struct p3d_vae {
   // default by measurement (MEASUREMENTS.md §14: 5.5 against 14.6 us per frame step at H3.6M size)
   int seq_form = 1, seq_len = 0, seq_xoff = 0, seq_toff = 0, seq_ldt = 0, seq_moff = 0;
   size_t seq_lds = 0;
+  // the wide form (in > 256; kernels in p3d_vae_wide.h): `desc` is then the core -- the filter
+  // behind layer 0, whose input is h0 [B, n0] -- and layer 0 (P0 = (in + 1) n0 floats) leads the
+  // flat buffers; the core's tensors follow at flat + P0.  Narrow: P0 = 0, Ptot = desc.P.
+  int wide = 0, in = 0, n0 = 0, P0 = 0, Ptot = 0;
+  std::vector<VaeTensor> tensors;       // the full parameter table (flat offsets into the master buffers)
+  int64_t h0_off = 0, dz0_off = 0;      // float offsets of h0 and dz0 in the workspace
 };
 
 namespace {
@@ -2705,6 +2712,34 @@ size_t vae_best_layout(VaeDesc& d, std::vector<std::string>& names, int in, int 
   return lds;
 }
 
+// The layout of any accepted shape: narrow as vae_best_layout; wide (in > 256) the core's layout
+// with layer 0 leading the names and the parameter table.  Returns the largest workgroup's LDS
+// (the wide kernels of layer 0 use none).
+size_t vae_full_layout(VaeDesc& d, std::vector<std::string>& names, std::vector<VaeTensor>& tensors, int& P0, int in,
+                       int n_enc, const int32_t* enc, int latent, int n_dec, const int32_t* dec, int out) {
+  tensors.clear();
+  P0 = 0;
+  if (in <= 256) {
+    const size_t lds = vae_best_layout(d, names, in, n_enc, enc, latent, n_dec, dec, out);
+    tensors.assign(d.T, d.T + d.nt);
+    return lds;
+  }
+  std::vector<std::string> core;
+  const size_t lds = vae_best_layout(d, core, enc[0], n_enc - 1, enc + 1, latent, n_dec, dec, out);
+  P0 = (in + 1) * enc[0];
+  const std::string s = "enc_h_" + std::to_string(enc[0]);
+  names = {s + "/kernel", s + "/bias"};
+  names.insert(names.end(), core.begin(), core.end());
+  tensors.push_back(VaeTensor{0, in, enc[0], -1, 0});
+  tensors.push_back(VaeTensor{in * enc[0], 1, enc[0], -1, 0});
+  for (int t = 0; t < d.nt; ++t) {
+    VaeTensor T = d.T[t];
+    T.flat += P0;
+    tensors.push_back(T);
+  }
+  return lds;
+}
+
 // The sequence filter's LDS behind the packed copy (float offsets): ONE tile's activation area, the
 // [16, in] state tile (the area's own input tile where the layout stages one), the frame's target
 // tile and the 16 rows' first frame (int64) and frame count (int).  Returns the dynamic LDS bytes.
@@ -2718,10 +2753,41 @@ size_t vae_seq_layout(const VaeDesc& d, int& xoff, int& toff, int& ldt, int& mof
   return sizeof(float) * ((size_t)d.Ppk + (size_t)act);
 }
 
-int vae_check_call(const p3d_vae* v, const float* x, int64_t B, const char* what) {
+int vae_check_call(const p3d_vae* v, const void* x, int64_t B, const char* what) {
   if (!v || !x) return fail(P3D_ERR_ARG, std::string(what) + ": null argument");
   if (B < 1 || B > (1 << 20)) return fail(P3D_ERR_ARG, std::string(what) + ": B must be in 1 .. 2^20");
   return P3D_OK;
+}
+
+// A caller's p3d_vae_cat checked against (in, B) and turned into the kernels' form.  Pure host code.
+int vae_cat_check(const p3d_vae_cat* c, int32_t in, int64_t B, const char* what, VaeCat* out) {
+  const std::string w(what);
+  if (!c) return fail(P3D_ERR_ARG, w + ": null argument");
+  if (c->n < 1 || c->n > 4) return fail(P3D_ERR_ARG, w + ": 1 to 4 segments");
+  VaeCat k{};
+  k.n = c->n;
+  int sum = 0;
+  for (int s = 0; s < c->n; ++s) {
+    if (c->w[s] < 8 || c->w[s] % 8 != 0) return fail(P3D_ERR_ARG, w + ": segment widths must be multiples of 8");
+    if (!c->p[s]) return fail(P3D_ERR_ARG, w + ": null segment pointer");
+    if ((uintptr_t)c->p[s] % 16 != 0) return fail(P3D_ERR_ARG, w + ": segments must be 16-byte aligned");
+    if (c->rows[s] < 1 || c->rows[s] > (INT64_MAX >> 16))
+      return fail(P3D_ERR_ARG, w + ": a segment's table needs at least one row");
+    if (!c->idx[s] && c->rows[s] < B) return fail(P3D_ERR_ARG, w + ": a segment without an index needs B rows");
+    k.w[s] = c->w[s]; k.off[s] = sum; k.p[s] = c->p[s]; k.idx[s] = c->idx[s]; k.rows[s] = c->rows[s];
+    sum += c->w[s];
+    if (sum > 2048) break;
+  }
+  if (in >= 0 && sum != in)   // (in < 0: no filter to compare with)
+    return fail(P3D_ERR_ARG, w + ": segment widths must sum to in (" + std::to_string(in) + ")");
+  if (out) *out = k;
+  return P3D_OK;
+}
+
+VaeCat vae_cat_plain(const float* x, int in, int64_t B) {
+  VaeCat k{};
+  k.n = 1; k.w[0] = in; k.p[0] = x; k.rows[0] = B;
+  return k;
 }
 
 VaeArgs vae_args(const p3d_vae* v, const float* x, const float* t, int64_t B, const float* eps, uint64_t ctr) {
@@ -2729,22 +2795,73 @@ VaeArgs vae_args(const p3d_vae* v, const float* x, const float* t, int64_t B, co
   a.desc = v->d_desc; a.pk = v->pk; a.x = x; a.t = t; a.eps = eps; a.B = B;
   a.seed = v->seed; a.ctr = ctr;
   a.ctr_dev = ctr == P3D_CTR_GLOBAL_STEP ? v->st : nullptr;
-  a.w = v->params; a.m = v->am; a.v = v->av; a.pk_out = v->pk; a.st = v->st;
+  a.w = v->params + v->P0; a.m = v->am + v->P0; a.v = v->av + v->P0; a.pk_out = v->pk; a.st = v->st;
   a.pkidx = v->pkidx;
   a.nblk = 1;
   return a;
 }
 
-// loss (backward = 0), gradient (backward = 1) or training step (adam = 1) over B rows
-int vae_step(p3d_vae* v, const float* x, const float* t, int64_t B, const float* eps, uint64_t ctr,
+VaeWideArgs vae_wide_args(const p3d_vae* v, const VaeCat& cat, int64_t B) {
+  VaeWideArgs wa{};
+  wa.cat = cat; wa.B = B; wa.in = v->in; wa.n0 = v->n0;
+  wa.w0 = v->params; wa.h0 = v->ws + v->h0_off; wa.dz0 = v->ws + v->dz0_off;
+  wa.g = v->grads; wa.w = v->params; wa.m = v->am; wa.v = v->av; wa.st = v->st;
+  return wa;
+}
+
+// the wide form's first launch: h0 = relu(x W0 + b0)
+int vae_wide_fwd(const p3d_vae* v, const VaeWideArgs& wa, hipStream_t st) {
+  const int64_t units = ((wa.B + 15) / 16) * ((v->n0 + 15) / 16);
+  const int64_t nwg = (units + 3) / 4, cap = (int64_t)v->cus * 8;
+  hipLaunchKernelGGL(k_vae_wide_fwd, dim3((unsigned)(nwg < cap ? nwg : cap)), dim3(256), 0, st, wa);
+  LAUNCH_CHECK("k_vae_wide_fwd");
+  return P3D_OK;
+}
+
+int vae_forward(p3d_vae* v, const float* x, const VaeCat* cat, int64_t B, const float* eps, uint64_t ctr, float* y,
+                float* mean, float* log_var, float* z, const float* target, float* row_terms, void* stream,
+                const char* what) {
+  if ((row_terms != nullptr) != (target != nullptr))
+    return fail(P3D_ERR_ARG, std::string(what) + ": row_terms and target go together");
+  const hipStream_t st = (hipStream_t)stream;
+  if (v->wide) {
+    if (B > v->max_batch) return fail(P3D_ERR_ARG, std::string(what) + ": B exceeds max_batch");
+    const VaeWideArgs wa = vae_wide_args(v, cat ? *cat : vae_cat_plain(x, v->in, B), B);
+    if (int rc = vae_wide_fwd(v, wa, st)) return rc;
+    x = wa.h0;
+    cat = nullptr;
+  }
+  VaeArgs a = vae_args(v, x, target, B, eps, ctr);
+  a.y = y; a.mean = mean; a.log_var = log_var; a.z = z; a.row_terms = row_terms;
+  if (cat) a.cat = *cat;
+  const int64_t nwg = (B + 63) / 64;
+  const int grid = (int)(nwg < v->cus ? nwg : v->cus);
+  if (cat) hipLaunchKernelGGL(k_vae_fwd_cat, dim3(grid), dim3(256), v->lds, st, a);
+  else hipLaunchKernelGGL(k_vae_fwd, dim3(grid), dim3(256), v->lds, st, a);
+  LAUNCH_CHECK("k_vae_fwd");
+  return P3D_OK;
+}
+
+// loss (backward = 0), gradient (backward = 1) or training step (adam = 1) over B rows; the input
+// is x or, where `cat` is set, the concatenated segments
+int vae_step(p3d_vae* v, const float* x, const VaeCat* cat, const float* t, int64_t B, const float* eps, uint64_t ctr,
              const float* factors, int backward, int adam, float lr, float* loss3, void* stream,
              const char* what) {
-  if (int rc = vae_check_call(v, x, B, what)) return rc;
   if (!t || !factors || !loss3) return fail(P3D_ERR_ARG, std::string(what) + ": null argument");
   if (B > v->max_batch) return fail(P3D_ERR_ARG, std::string(what) + ": B exceeds max_batch");
   if (factors[1] != 0.0f && v->desc.out != 48)
     return fail(P3D_ERR_ARG, std::string(what) + ": the KCS term needs out == 48 (kcs_factor must be 0)");
+  const hipStream_t st = (hipStream_t)stream;
+  VaeWideArgs wa{};
+  if (v->wide) {
+    wa = vae_wide_args(v, cat ? *cat : vae_cat_plain(x, v->in, B), B);
+    wa.adam = adam;
+    if (int rc = vae_wide_fwd(v, wa, st)) return rc;
+    x = wa.h0;
+    cat = nullptr;
+  }
   VaeArgs a = vae_args(v, x, t, B, eps, ctr);
+  if (cat) a.cat = *cat;
   const int nblk = (int)((B + 63) / 64);
   const bool one = nblk == 1 && v->form == 0;
   a.backward = backward; a.adam = adam; a.lr = lr;
@@ -2755,16 +2872,25 @@ int vae_step(p3d_vae* v, const float* x, const float* t, int64_t B, const float*
   for (int j = 0; j < 3; ++j) a.f[j] = factors[j];
   a.lpart = v->ws + (int64_t)nblk * v->desc.P;
   a.loss3 = loss3;
-  a.gout = one ? v->grads : v->ws;
+  a.gout = one ? v->grads + v->P0 : v->ws;
   a.tail = one;
-  const hipStream_t st = (hipStream_t)stream;
+  a.dx = v->wide ? v->ws + v->dz0_off : nullptr;
   const int grid = nblk < v->cus ? nblk : v->cus;
-  hipLaunchKernelGGL(k_vae_step, dim3(grid), dim3(256), v->lds, st, a);
+  if (v->wide) hipLaunchKernelGGL(k_vae_step_dx, dim3(grid), dim3(256), v->lds, st, a);
+  else if (cat) hipLaunchKernelGGL(k_vae_step_cat, dim3(grid), dim3(256), v->lds, st, a);
+  else hipLaunchKernelGGL(k_vae_step, dim3(grid), dim3(256), v->lds, st, a);
   LAUNCH_CHECK("k_vae_step");
-  if (one) return P3D_OK;
-  // the partials form: block sums (gradient and loss) and the optimizer, behind it on the stream
-  hipLaunchKernelGGL(k_vae_reduce_adam, dim3(backward ? (v->desc.P + 255) / 256 : 1), dim3(256), 0, st, a, v->grads);
-  LAUNCH_CHECK("k_vae_reduce_adam");
+  if (!one) {
+    // the partials form: block sums (gradient and loss) and the optimizer, behind it on the stream
+    hipLaunchKernelGGL(k_vae_reduce_adam, dim3(backward ? (v->desc.P + 255) / 256 : 1), dim3(256), 0, st, a,
+                       v->grads + v->P0);
+    LAUNCH_CHECK("k_vae_reduce_adam");
+  }
+  if (v->wide && backward) {   // layer 0's gradient (and optimizer), behind dz0 and alpha on the stream
+    const int units = ((v->in + 15) / 16 + 1) * ((v->n0 + 15) / 16);
+    hipLaunchKernelGGL(k_vae_wide_wgrad_adam, dim3((units + 3) / 4), dim3(256), 0, st, wa);
+    LAUNCH_CHECK("k_vae_wide_wgrad_adam");
+  }
   return P3D_OK;
 }
 
@@ -2775,7 +2901,7 @@ int vae_check_shape(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t 
                     const int32_t* dec_dims, int32_t out) {
   if (!enc_dims || !dec_dims) return fail(P3D_ERR_ARG, "p3d_vae_create: null argument");
   auto width = [](int w, int hi) { return w >= 8 && w <= hi && w % 8 == 0; };
-  if (!width(in, 256)) return fail(P3D_ERR_ARG, "p3d_vae_create: in must be a multiple of 8 in 8 .. 256");
+  if (!width(in, 2048)) return fail(P3D_ERR_ARG, "p3d_vae_create: in must be a multiple of 8 in 8 .. 2048");
   if (n_enc < 1 || n_enc > 4 || n_dec < 1 || n_dec > 4)
     return fail(P3D_ERR_ARG, "p3d_vae_create: 1 to 4 hidden layers on each side");
   for (int e = 0; e < n_enc; ++e)
@@ -2793,7 +2919,9 @@ extern "C" int64_t p3d_vae_lds_bytes(int32_t in, int32_t n_enc, const int32_t* e
   if (vae_check_shape(in, n_enc, enc_dims, latent, n_dec, dec_dims, out)) return 0;
   VaeDesc d;
   std::vector<std::string> names;
-  return (int64_t)vae_best_layout(d, names, in, n_enc, enc_dims, latent, n_dec, dec_dims, out);
+  std::vector<VaeTensor> tensors;
+  int P0;
+  return (int64_t)vae_full_layout(d, names, tensors, P0, in, n_enc, enc_dims, latent, n_dec, dec_dims, out);
 }
 
 extern "C" int p3d_vae_create(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent, int32_t n_dec,
@@ -2802,7 +2930,10 @@ extern "C" int p3d_vae_create(int32_t in, int32_t n_enc, const int32_t* enc_dims
   if (int rc = vae_check_shape(in, n_enc, enc_dims, latent, n_dec, dec_dims, out)) return rc;
   if (max_batch < 1 || max_batch > (1 << 20)) return fail(P3D_ERR_ARG, "p3d_vae_create: max_batch must be in 1 .. 2^20");
   p3d_vae* v = new p3d_vae();
-  v->lds = vae_best_layout(v->desc, v->names, in, n_enc, enc_dims, latent, n_dec, dec_dims, out);
+  v->lds = vae_full_layout(v->desc, v->names, v->tensors, v->P0, in, n_enc, enc_dims, latent, n_dec, dec_dims, out);
+  v->wide = in > 256;
+  v->in = in; v->n0 = enc_dims[0];
+  v->Ptot = v->P0 + v->desc.P;
   if (v->lds > P3D_VAE_LDS_LIMIT) {
     const size_t need = v->lds;
     delete v;
@@ -2821,6 +2952,11 @@ extern "C" int p3d_vae_create(int32_t in, int32_t n_enc, const int32_t* enc_dims
   v->seed = seed;
   const int64_t nblk = (max_batch + 63) / 64;
   v->ws_floats = nblk * ((int64_t)v->desc.P + 4) + 4;
+  if (v->wide) {   // h0 and dz0 behind the core's block partials (offsets fixed by max_batch, multiples of 4)
+    v->h0_off = v->ws_floats;
+    v->dz0_off = v->h0_off + (int64_t)max_batch * v->n0;
+    v->ws_floats = v->dz0_off + (int64_t)max_batch * v->n0;
+  }
   auto bail = [&](hipError_t e, const char* what) {
     p3d_vae_destroy(v);
     return fail(P3D_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
@@ -2831,7 +2967,7 @@ extern "C" int p3d_vae_create(int32_t in, int32_t n_enc, const int32_t* enc_dims
   hipDeviceProp_t prop;
   if ((e = hipGetDeviceProperties(&prop, dev)) != hipSuccess) return bail(e, "hipGetDeviceProperties");
   v->cus = prop.multiProcessorCount;
-  const size_t pb = sizeof(float) * (size_t)v->desc.P;
+  const size_t pb = sizeof(float) * (size_t)v->Ptot;
   float** bufs[4] = {&v->params, &v->grads, &v->am, &v->av};
   for (auto b : bufs) {
     if ((e = hipMalloc((void**)b, pb)) != hipSuccess) return bail(e, "hipMalloc");
@@ -2861,7 +2997,10 @@ extern "C" int p3d_vae_create(int32_t in, int32_t n_enc, const int32_t* enc_dims
     return bail(e, "hipFuncSetAttribute(k_vae_fwd)");
   if ((e = hipFuncSetAttribute((const void*)k_vae_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->lds)) != hipSuccess)
     return bail(e, "hipFuncSetAttribute(k_vae_step)");
-  if (in % out == 0 && in / out <= P3D_VAE_SEQ_MAX_LEN) {
+  for (const void* k : {(const void*)k_vae_fwd_cat, (const void*)k_vae_step_cat, (const void*)k_vae_step_dx})
+    if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->lds)) != hipSuccess)
+      return bail(e, "hipFuncSetAttribute(k_vae_*_cat)");
+  if (!v->wide && in % out == 0 && in / out <= P3D_VAE_SEQ_MAX_LEN) {
     const size_t sl = vae_seq_layout(v->desc, v->seq_xoff, v->seq_toff, v->seq_ldt, v->seq_moff);
     if (sl <= P3D_VAE_LDS_LIMIT) {
       v->seq_len = in / out;
@@ -2887,15 +3026,15 @@ extern "C" int p3d_vae_destroy(p3d_vae* v) {
 
 extern "C" int p3d_vae_param_count(const p3d_vae* v, int32_t* count) {
   if (!v || !count) return fail(P3D_ERR_ARG, "p3d_vae_param_count: null argument");
-  *count = v->desc.nt;
+  *count = (int32_t)v->tensors.size();
   return P3D_OK;
 }
 
 extern "C" int p3d_vae_param_info(const p3d_vae* v, int32_t idx, const char** name, int64_t* numel, int32_t* rows,
                                   int32_t* cols, int64_t* offset) {
   if (!v) return fail(P3D_ERR_ARG, "p3d_vae_param_info: null argument");
-  if (idx < 0 || idx >= v->desc.nt) return fail(P3D_ERR_ARG, "p3d_vae_param_info: index out of range");
-  const VaeTensor& T = v->desc.T[idx];
+  if (idx < 0 || idx >= (int)v->tensors.size()) return fail(P3D_ERR_ARG, "p3d_vae_param_info: index out of range");
+  const VaeTensor& T = v->tensors[idx];
   if (name) *name = v->names[idx].c_str();
   if (numel) *numel = (int64_t)T.K * T.N;
   if (rows) *rows = T.K;
@@ -2906,10 +3045,10 @@ extern "C" int p3d_vae_param_info(const p3d_vae* v, int32_t idx, const char** na
 
 extern "C" int p3d_vae_param_ptr(p3d_vae* v, const char* name, void** dptr, int64_t* numel) {
   if (!v || !name || !dptr) return fail(P3D_ERR_ARG, "p3d_vae_param_ptr: null argument");
-  for (int i = 0; i < v->desc.nt; ++i)
+  for (size_t i = 0; i < v->tensors.size(); ++i)
     if (v->names[i] == name) {
-      *dptr = v->params + v->desc.T[i].flat;
-      if (numel) *numel = (int64_t)v->desc.T[i].K * v->desc.T[i].N;
+      *dptr = v->params + v->tensors[i].flat;
+      if (numel) *numel = (int64_t)v->tensors[i].K * v->tensors[i].N;
       return P3D_OK;
     }
   return fail(P3D_ERR_NOTFOUND, std::string("p3d_vae_param_ptr: no parameter named ") + name);
@@ -2920,57 +3059,105 @@ extern "C" int p3d_vae_flat_ptr(p3d_vae* v, int32_t which, void** dptr, int64_t*
   float* const bufs[6] = {v->params, v->grads, v->am, v->av, v->ws, v->pk};
   if (which < 0 || which > 5) return fail(P3D_ERR_ARG, "p3d_vae_flat_ptr: which must be 0 .. 5");
   *dptr = bufs[which];
-  if (numel) *numel = which == 4 ? v->ws_floats : which == 5 ? v->desc.Ppk : v->desc.P;
+  if (numel) *numel = which == 4 ? v->ws_floats : which == 5 ? v->desc.Ppk : v->Ptot;
   return P3D_OK;
 }
 
 extern "C" int p3d_vae_params_updated(p3d_vae* v, void* stream) {
   if (!v) return fail(P3D_ERR_ARG, "p3d_vae_params_updated: null argument");
   hipLaunchKernelGGL(k_vae_pack, dim3((v->desc.P + 255) / 256), dim3(256), 0, (hipStream_t)stream, v->desc.P,
-                     (const int*)v->pkidx, (const float*)v->params, v->pk);
+                     (const int*)v->pkidx, (const float*)(v->params + v->P0), v->pk);
   LAUNCH_CHECK("k_vae_pack");
   return P3D_OK;
+}
+
+extern "C" int p3d_vae_cat_check(const p3d_vae_cat* cat, int32_t in, int64_t B) {
+  if (B < 1 || B > (1 << 20)) return fail(P3D_ERR_ARG, "p3d_vae_cat_check: B must be in 1 .. 2^20");
+  return vae_cat_check(cat, in, B, "p3d_vae_cat_check", nullptr);
 }
 
 extern "C" int p3d_vae_forward(p3d_vae* v, const float* x, int64_t B, const float* eps, uint64_t ctr, float* y,
                                float* mean, float* log_var, float* z, const float* target, float* row_terms,
                                void* stream) {
   if (int rc = vae_check_call(v, x, B, "p3d_vae_forward")) return rc;
-  if ((row_terms != nullptr) != (target != nullptr))
-    return fail(P3D_ERR_ARG, "p3d_vae_forward: row_terms and target go together");
-  VaeArgs a = vae_args(v, x, target, B, eps, ctr);
-  a.y = y; a.mean = mean; a.log_var = log_var; a.z = z; a.row_terms = row_terms;
-  const int64_t nwg = (B + 63) / 64;
-  const int grid = (int)(nwg < v->cus ? nwg : v->cus);
-  hipLaunchKernelGGL(k_vae_fwd, dim3(grid), dim3(256), v->lds, (hipStream_t)stream, a);
-  LAUNCH_CHECK("k_vae_fwd");
-  return P3D_OK;
+  return vae_forward(v, x, nullptr, B, eps, ctr, y, mean, log_var, z, target, row_terms, stream, "p3d_vae_forward");
 }
 
 extern "C" int p3d_vae_loss(p3d_vae* v, const float* x, const float* t, int64_t B, const float* eps, uint64_t ctr,
                             const float* factors, float* loss3_dev, void* stream) {
-  return vae_step(v, x, t, B, eps, ctr, factors, 0, 0, 0.0f, loss3_dev, stream, "p3d_vae_loss");
+  if (int rc = vae_check_call(v, x, B, "p3d_vae_loss")) return rc;
+  return vae_step(v, x, nullptr, t, B, eps, ctr, factors, 0, 0, 0.0f, loss3_dev, stream, "p3d_vae_loss");
 }
 
 extern "C" int p3d_vae_grad(p3d_vae* v, const float* x, const float* t, int64_t B, const float* eps, uint64_t ctr,
                             const float* factors, float* loss3_dev, void* stream) {
-  return vae_step(v, x, t, B, eps, ctr, factors, 1, 0, 0.0f, loss3_dev, stream, "p3d_vae_grad");
+  if (int rc = vae_check_call(v, x, B, "p3d_vae_grad")) return rc;
+  return vae_step(v, x, nullptr, t, B, eps, ctr, factors, 1, 0, 0.0f, loss3_dev, stream, "p3d_vae_grad");
 }
 
 extern "C" int p3d_vae_train_step(p3d_vae* v, const float* x, const float* t, int64_t B, const float* eps,
                                   const float* factors, float lr, float* loss3_dev, void* stream) {
   if (!(lr >= 0.0f)) return fail(P3D_ERR_ARG, "p3d_vae_train_step: lr must be >= 0");
-  return vae_step(v, x, t, B, eps, P3D_CTR_GLOBAL_STEP, factors, 1, 1, lr, loss3_dev, stream, "p3d_vae_train_step");
+  if (int rc = vae_check_call(v, x, B, "p3d_vae_train_step")) return rc;
+  return vae_step(v, x, nullptr, t, B, eps, P3D_CTR_GLOBAL_STEP, factors, 1, 1, lr, loss3_dev, stream,
+                  "p3d_vae_train_step");
+}
+
+// The _cat twins.  The struct's own errors answer first: they need no filter (and no GPU).
+namespace {
+int vae_cat_call(const p3d_vae* v, const p3d_vae_cat* cat, int64_t B, const char* what, VaeCat* k) {
+  if (!cat) return fail(P3D_ERR_ARG, std::string(what) + ": null argument");
+  if (B < 1 || B > (1 << 20)) return fail(P3D_ERR_ARG, std::string(what) + ": B must be in 1 .. 2^20");
+  if (int rc = vae_cat_check(cat, v ? v->in : -1, B, what, k)) return rc;
+  return vae_check_call(v, cat, B, what);
+}
+}  // namespace
+
+extern "C" int p3d_vae_forward_cat(p3d_vae* v, const p3d_vae_cat* cat, int64_t B, const float* eps, uint64_t ctr,
+                                   float* y, float* mean, float* log_var, float* z, const float* target,
+                                   float* row_terms, void* stream) {
+  VaeCat k;
+  if (int rc = vae_cat_call(v, cat, B, "p3d_vae_forward_cat", &k)) return rc;
+  return vae_forward(v, nullptr, &k, B, eps, ctr, y, mean, log_var, z, target, row_terms, stream, "p3d_vae_forward_cat");
+}
+
+extern "C" int p3d_vae_loss_cat(p3d_vae* v, const p3d_vae_cat* cat, const float* t, int64_t B, const float* eps,
+                                uint64_t ctr, const float* factors, float* loss3_dev, void* stream) {
+  VaeCat k;
+  if (int rc = vae_cat_call(v, cat, B, "p3d_vae_loss_cat", &k)) return rc;
+  return vae_step(v, nullptr, &k, t, B, eps, ctr, factors, 0, 0, 0.0f, loss3_dev, stream, "p3d_vae_loss_cat");
+}
+
+extern "C" int p3d_vae_grad_cat(p3d_vae* v, const p3d_vae_cat* cat, const float* t, int64_t B, const float* eps,
+                                uint64_t ctr, const float* factors, float* loss3_dev, void* stream) {
+  VaeCat k;
+  if (int rc = vae_cat_call(v, cat, B, "p3d_vae_grad_cat", &k)) return rc;
+  return vae_step(v, nullptr, &k, t, B, eps, ctr, factors, 1, 0, 0.0f, loss3_dev, stream, "p3d_vae_grad_cat");
+}
+
+extern "C" int p3d_vae_train_step_cat(p3d_vae* v, const p3d_vae_cat* cat, const float* t, int64_t B, const float* eps,
+                                      const float* factors, float lr, float* loss3_dev, void* stream) {
+  if (!(lr >= 0.0f)) return fail(P3D_ERR_ARG, "p3d_vae_train_step_cat: lr must be >= 0");
+  VaeCat k;
+  if (int rc = vae_cat_call(v, cat, B, "p3d_vae_train_step_cat", &k)) return rc;
+  return vae_step(v, nullptr, &k, t, B, eps, P3D_CTR_GLOBAL_STEP, factors, 1, 1, lr, loss3_dev, stream,
+                  "p3d_vae_train_step_cat");
 }
 
 extern "C" int p3d_vae_adam_apply(p3d_vae* v, float lr, void* stream) {
   if (!v || !(lr >= 0.0f)) return fail(P3D_ERR_ARG, "p3d_vae_adam_apply: bad argument");
   VaeArgs a = vae_args(v, nullptr, nullptr, 1, nullptr, 0);
-  a.backward = 1; a.adam = 1; a.nblk = 1; a.gout = v->grads; a.loss3 = nullptr;
+  a.backward = 1; a.adam = 1; a.nblk = 1; a.gout = v->grads + v->P0; a.loss3 = nullptr;
   hipLaunchKernelGGL(k_vae_alpha, dim3(1), dim3(1), 0, (hipStream_t)stream, v->st, lr);
   LAUNCH_CHECK("k_vae_alpha");
-  hipLaunchKernelGGL(k_vae_reduce_adam, dim3((v->desc.P + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, v->grads);
+  hipLaunchKernelGGL(k_vae_reduce_adam, dim3((v->desc.P + 255) / 256), dim3(256), 0, (hipStream_t)stream, a,
+                     v->grads + v->P0);
   LAUNCH_CHECK("k_vae_reduce_adam");
+  if (v->wide) {
+    hipLaunchKernelGGL(k_vae_wide_adam, dim3((v->P0 + 255) / 256), dim3(256), 0, (hipStream_t)stream, v->P0,
+                       (const float*)v->grads, v->params, v->am, v->av, (const VaeState*)v->st);
+    LAUNCH_CHECK("k_vae_wide_adam");
+  }
   return P3D_OK;
 }
 
@@ -3013,7 +3200,7 @@ extern "C" int64_t p3d_vae_seq_lds_bytes(int32_t in, int32_t n_enc, const int32_
                                          int32_t n_dec, const int32_t* dec_dims, int32_t out, int32_t form) {
   if (form != 0 && form != 1) return 0;
   if (vae_check_shape(in, n_enc, enc_dims, latent, n_dec, dec_dims, out)) return 0;
-  if (in % out != 0 || in / out > P3D_VAE_SEQ_MAX_LEN) return 0;
+  if (in > 256 || in % out != 0 || in / out > P3D_VAE_SEQ_MAX_LEN) return 0;
   VaeDesc d;
   std::vector<std::string> names;
   if (vae_best_layout(d, names, in, n_enc, enc_dims, latent, n_dec, dec_dims, out) > P3D_VAE_LDS_LIMIT) return 0;
@@ -3032,7 +3219,7 @@ extern "C" int p3d_vae_seq_filter(p3d_vae* v, const float* pred, const int64_t* 
                                   float* state, int32_t* started, float* ref, float* frame_err, double* seq_err,
                                   void* stream) {
   if (!v || !pred || !seq_off || !ref) return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: null argument");
-  if (v->desc.in % v->desc.out != 0 || v->desc.in / v->desc.out > P3D_VAE_SEQ_MAX_LEN)
+  if (v->wide || v->desc.in % v->desc.out != 0 || v->desc.in / v->desc.out > P3D_VAE_SEQ_MAX_LEN)
     return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: in must be seq_len * out with seq_len in 1 .. " +
                                  std::to_string(P3D_VAE_SEQ_MAX_LEN));
   if (!v->seq_lds)
@@ -3062,7 +3249,7 @@ extern "C" int p3d_vae_seq_filter(p3d_vae* v, const float* pred, const int64_t* 
 extern "C" int64_t p3d_vae_workspace(const p3d_vae* v, int64_t B) {
   if (!v || B < 1) return 0;
   const int64_t nblk = (B + 63) / 64;
-  return (int64_t)sizeof(float) * (nblk * ((int64_t)v->desc.P + 4) + 4);
+  return (int64_t)sizeof(float) * (nblk * ((int64_t)v->desc.P + 4) + 4 + (v->wide ? 2 * B * v->n0 : 0));
 }
 
 #include "p3d_dp.h"

@@ -26,6 +26,11 @@
 // step); at B > 64 every 64-row block writes its partial gradient to the workspace and
 // k_vae_reduce_adam, ordered behind it by the stream alone, sums the blocks and applies Adam.  No
 // kernel here waits on another workgroup.
+//
+// The kernels come in forms of one body: k_vae_fwd_cat / k_vae_step_cat read the input through a
+// VaeCat (column segments, each optionally row-indexed; p3d.h p3d_vae_cat) instead of x, in the
+// same order of operations; k_vae_step_dx is the core of the wide form (p3d_vae_wide.h), whose
+// input is layer 0's output and whose backward also leaves the data gradient at that input.
 #pragma once
 #include "p3d_kernels.h"
 #include "p3d_layers.h"   // p3d_adam1
@@ -109,6 +114,34 @@ __device__ __forceinline__ float vae_rowsum4(float v) {
   return v;
 }
 
+// The input as 1 .. 4 column segments, each a table [rows, w] read at row r or at row idx[r]
+// (p3d.h p3d_vae_cat); off[s] = w[0] + .. + w[s - 1].
+struct VaeCat {
+  int n;
+  int w[4], off[4];
+  const float* p[4];
+  const int64_t* idx[4];
+  int64_t rows[4];
+};
+
+// Element (row, col) of the concatenated input.  An index is clamped into its table: a bad one
+// never becomes a wild read.  (Unrolled selects: no dynamic index into the kernel arguments.)
+__device__ __forceinline__ const float* vae_cat_at(const VaeCat& c, int64_t row, int col) {
+  const float* p = c.p[0];
+  const int64_t* ix = c.idx[0];
+  int64_t rows = c.rows[0];
+  int w = c.w[0], off = 0;
+#pragma unroll
+  for (int s = 1; s < 4; ++s)
+    if (s < c.n && col >= c.off[s]) { p = c.p[s]; ix = c.idx[s]; rows = c.rows[s]; w = c.w[s]; off = c.off[s]; }
+  int64_t r = row;
+  if (ix) {
+    r = ix[row];
+    r = r < 0 ? 0 : (r > rows - 1 ? rows - 1 : r);
+  }
+  return p + r * w + (col - off);
+}
+
 struct VaeArgs {
   const VaeDesc* desc;
   const float* pk;            // packed parameters [Ppk]
@@ -131,6 +164,8 @@ struct VaeArgs {
   float* loss3;               // one-launch forms: the loss 3-vector
   float* w; float* m; float* v; float* pk_out; VaeState* st;
   const int* pkidx;           // flat element -> its place in the packed copy
+  float* dx;                  // k_vae_step_dx: d(loss sum) / dx, [B, in]
+  VaeCat cat;                 // the _cat kernels: the input in place of x
 };
 
 // One layer of one 16-row tile: out = act(A W + b).  `arow` is this lane's row of A (global x or
@@ -157,10 +192,36 @@ __device__ __forceinline__ void vae_layer_fwd(const VaeLayer& L, const float* ar
   }
 }
 
+// Layer 0 of one tile on a concatenated input that is not staged in LDS: the same k order, each
+// operand through vae_cat_at.
+__device__ __forceinline__ void vae_layer_fwd_cat(const VaeLayer& L, const VaeCat& c, int64_t row, const float* W,
+                                                  float* out) {
+  const int lane = threadIdx.x & 63, i = lane & 15, q = lane >> 4;
+  const int K = L.K, ld = L.ld, ldo = L.ldo, relu = L.relu, nct = L.Np >> 4;
+  for (int ct = 0; ct < nct; ++ct) {
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    const float* wp = W + L.wpk + q * ld + 16 * ct + i;
+    for (int k = 0; k < K; k += 8) {
+      const float a0 = *vae_cat_at(c, row, k + q), b0 = wp[k * ld];
+      const float a1 = *vae_cat_at(c, row, k + 4 + q), b1 = wp[(k + 4) * ld];
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc, 0, 0, 0);
+    }
+    const float b = W[L.bpk + 16 * ct + i];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float v = acc[r] + b;
+      if (relu) v = fmaxf(v, 0.0f);
+      out[(4 * q + r) * ldo + 16 * ct + i] = v;
+    }
+  }
+}
+
 // Forward of one tile (rows row0 .. row0 + 15) through every layer, the reparametrisation, the
 // requested global outputs and the three per-row loss terms (when a.t is set); with `train` also
 // 0.5 eps std, and dy = d(loss sum) / dy in place of y.  Returns this lane's row terms (lanes of
 // one row hold the same values).
+template <bool CAT>
 __device__ __forceinline__ void vae_tile_fwd(const VaeArgs& a, const VaeDesc* d, const float* W, float* act,
                                              int64_t row0, uint64_t ctr, bool train, float terms[3]) {
   const int lane = threadIdx.x & 63, i = lane & 15, q = lane >> 4;
@@ -175,10 +236,12 @@ __device__ __forceinline__ void vae_tile_fwd(const VaeArgs& a, const VaeDesc* d,
     for (int idx = lane; idx < 16 * in; idx += 64) {
       const int r = idx / in, c = idx - r * in;
       const int64_t grow = row0 + r < a.B ? row0 + r : Bm1;
-      xb[r * ldx + c] = a.x[grow * in + c];
+      xb[r * ldx + c] = CAT ? *vae_cat_at(a.cat, grow, c) : a.x[grow * in + c];
     }
     vae_wsync();
     vae_layer_fwd(d->L[0], xb + i * ldx, W, act + d->L[0].aout);
+  } else if (CAT) {
+    vae_layer_fwd_cat(d->L[0], a.cat, myrow, W, act + d->L[0].aout);
   } else {
     vae_layer_fwd(d->L[0], a.x + myrow * d->in, W, act + d->L[0].aout);
   }
@@ -350,7 +413,8 @@ __device__ __forceinline__ void vae_load_params(const VaeArgs& a, const VaeDesc*
 
 // The filter: x -> mean, log_var -> z -> y, every output optional.  Waves stride over the 16-row
 // tiles on their own: no barrier after the parameter load.
-__global__ __launch_bounds__(256) void k_vae_fwd(VaeArgs a) {
+template <bool CAT>
+__device__ __forceinline__ void vae_fwd_body(const VaeArgs& a) {
   extern __shared__ f32x4 vae_smem[];
   float* sm = (float*)vae_smem;
   const VaeDesc* d = a.desc;
@@ -361,7 +425,7 @@ __global__ __launch_bounds__(256) void k_vae_fwd(VaeArgs a) {
   const int64_t ntiles = (a.B + 15) >> 4;
   for (int64_t tile = (int64_t)blockIdx.x * 4 + wave; tile < ntiles; tile += (int64_t)gridDim.x * 4) {
     float terms[3];
-    vae_tile_fwd(a, d, sm, act, tile * 16, ctr, false, terms);
+    vae_tile_fwd<CAT>(a, d, sm, act, tile * 16, ctr, false, terms);
     const int64_t row = tile * 16 + (lane & 15);
     if (a.row_terms && a.t && lane < 16 && row < a.B) {
       a.row_terms[row * 3 + 0] = terms[0];
@@ -371,6 +435,8 @@ __global__ __launch_bounds__(256) void k_vae_fwd(VaeArgs a) {
     vae_wsync();
   }
 }
+__global__ __launch_bounds__(256) void k_vae_fwd(VaeArgs a) { vae_fwd_body<false>(a); }
+__global__ __launch_bounds__(256) void k_vae_fwd_cat(VaeArgs a) { vae_fwd_body<true>(a); }
 
 __device__ __forceinline__ float vae_alpha(const VaeState* st, float lr) {
 #pragma clang fp contract(off)
@@ -432,7 +498,11 @@ __device__ __forceinline__ void vae_loss3(const VaeArgs& a, int j) {
 
 // The training step: forward, the three loss terms, backward to every parameter's gradient and --
 // in the one-workgroup form (nblk == 1, a.adam) -- Adam and the new packed copy.
-__global__ __launch_bounds__(256) void k_vae_step(VaeArgs a) {
+// CAT: the input through a.cat.  DX (the wide form's core, whose input is layer 0's ReLU output):
+// the data gradient runs for layer 0 too and goes to a.dx; alpha is always left
+// in the state for the layer-0 optimizer behind this launch.
+template <bool CAT, bool DX>
+__device__ __forceinline__ void vae_step_body(const VaeArgs& a) {
   extern __shared__ f32x4 vae_smem[];
   float* sm = (float*)vae_smem;
   const VaeDesc* d = a.desc;
@@ -445,13 +515,13 @@ __global__ __launch_bounds__(256) void k_vae_step(VaeArgs a) {
   float alpha = 0.0f;
   if (a.adam) {
     alpha = vae_alpha(a.st, a.lr);
-    if (!a.tail && blockIdx.x == 0 && tid == 0) a.st->alpha = alpha;   // for k_vae_reduce_adam
+    if ((DX || !a.tail) && blockIdx.x == 0 && tid == 0) a.st->alpha = alpha;   // for k_vae_reduce_adam
   }
   const int nl = d->nl;
   for (int blk = blockIdx.x; blk < a.nblk; blk += gridDim.x) {
     const int64_t row0 = (int64_t)blk * 64 + wave * 16;
     float terms[3];
-    vae_tile_fwd(a, d, sm, act, row0, ctr, a.backward != 0, terms);
+    vae_tile_fwd<CAT>(a, d, sm, act, row0, ctr, a.backward != 0, terms);
     if (lane < 16) {
       const bool valid = row0 + i < a.B;
 #pragma unroll
@@ -481,7 +551,8 @@ __global__ __launch_bounds__(256) void k_vae_step(VaeArgs a) {
               for (int s = 0; s < 4; ++s) {
                 int64_t row = (int64_t)blk * 64 + 16 * t + 4 * s + q;
                 row = row < a.B ? row : a.B - 1;   // (dz is zero on rows past B)
-                const float xv = a.x[row * d->in + (kc < L.K ? kc : L.K - 1)];
+                const int xc = kc < L.K ? kc : L.K - 1;
+                const float xv = CAT ? *vae_cat_at(a.cat, row, xc) : a.x[row * d->in + xc];
                 const float av = kc < L.K ? xv : 0.0f;
                 acc =__builtin_amdgcn_mfma_f32_16x16x4f32(av, zt[(4 * s + q) * L.ldo + 16 * nt + i], acc, 0, 0, 0);
               }
@@ -560,6 +631,30 @@ __global__ __launch_bounds__(256) void k_vae_step(VaeArgs a) {
           __syncthreads();   // every wave's dz of the layer below is written
         }
       }
+      if (DX) {   // layer 0's da = dz W^T (the loop's own data-gradient arithmetic) leaves for the layer-0 weight gradient
+        const VaeLayer& L = d->L[0];
+        const float* ap = act + L.aout + i * L.ldo + q;
+        const int N = L.N, din = d->in;
+        for (int kt = 0; kt < ((L.K + 15) >> 4); ++kt) {
+          const int kc = 16 * kt + i;
+          const bool inK = kc < L.K;
+          const float* wp = sm + L.wpk + (inK ? kc : L.K - 1) * L.ld + q;
+          f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+          for (int n = 0; n < N; n += 8) {
+            const float a0 = ap[n], w0 = wp[n], a1 = ap[n + 4], w1 = wp[n + 4];
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, inK ? w0 : 0.0f, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, inK ? w1 : 0.0f, acc, 0, 0, 0);
+          }
+          if (inK) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int64_t grow = row0 + 4 * q + r;
+              if (grow < a.B) a.dx[grow * din + kc] = acc[r];
+            }
+          }
+        }
+        __syncthreads();   // (the next block's forward overwrites the activations)
+      }
     }
   }
   if (a.tail) {   // one-launch forms: the loss, and the optimizer behind the gradient
@@ -573,6 +668,9 @@ __global__ __launch_bounds__(256) void k_vae_step(VaeArgs a) {
     }
   }
 }
+__global__ __launch_bounds__(256) void k_vae_step(VaeArgs a) { vae_step_body<false, false>(a); }
+__global__ __launch_bounds__(256) void k_vae_step_cat(VaeArgs a) { vae_step_body<true, false>(a); }
+__global__ __launch_bounds__(256) void k_vae_step_dx(VaeArgs a) { vae_step_body<false, true>(a); }
 
 // B > 64: block partials summed in block order into the gradient buffer, then Adam.  Also the
 // stand-alone optimizer over the gradient buffer (nblk == 1, partials == the buffer itself).

@@ -42,6 +42,12 @@ def build_parser():
     p.add_argument("--noise_3d", type=float, nargs=2, default=[1, 1],
                    help="Noise added for 3d points, second value is a noise added over a single joint")
     p.add_argument("--evaluate", action='store_true', default=False, help="Set to True for evaluating.")
+    p.add_argument("--use_effb1", action='store_true', default=False,
+                   help="Use Efficient Net B1 instead of B0 (accepted and ignored: the features are read "
+                        "precomputed, whatever model made them)")
+    p.add_argument("--effnet_outputs_path", type=str, default="data/human36m_effnet.hdf5",
+                   help="File path for the outputs of the efficientNet model (.hdf5, or an .npz archive whose "
+                        "member names are the dataset paths)")
     # build-specific: where evaluate() of 3d_pose_vae_filter_kin.py reads the filter's weights
     p.add_argument("--vae_weights", type=str, default=None,
                    help="The .npz of VAE weights that --evaluate loads (default: the one train() saves)")

@@ -99,3 +99,48 @@ def window_y(split, idx=None):
     """[len(idx), 48] targets: every window's last frame."""
     starts = split["starts"] if idx is None else split["starts"][idx]
     return split["frames"][starts + split["seq_len"] - 1]
+
+
+def load_effnet_outputs(path, order_keys, sizes):
+    """The precomputed EfficientNet features of the frames behind `order_keys`, concatenated in key
+    order (load_effnet_h5py_outputs, data_handler.py:325-340): per key (subject, action, name) the
+    dataset ``<subject>/<action>/<name without .h5>/data``, cut to the key's 2D frame count `size`
+    (some frames have no 2D pose).  `path` is an ``.npz`` archive whose member names are those
+    dataset paths (the archive convention of data_utils), or the reference's ``.hdf5`` file where
+    h5py is installed.  A missing dataset or one shorter than `size` raises ValueError naming the key."""
+    order_keys, sizes = list(order_keys), [int(n) for n in sizes]
+    if len(order_keys) != len(sizes):
+        raise ValueError("load_effnet_outputs: %d keys but %d sizes" % (len(order_keys), len(sizes)))
+    if str(path).endswith(".npz"):
+        src = np.load(path, allow_pickle=False)
+        names = set(src.files)
+
+        def read(rel):
+            return np.asarray(src[rel]) if rel in names else None
+    else:
+        try:
+            import h5py
+        except ImportError:
+            raise ImportError("reading %s needs h5py; pass the features as an .npz archive whose member names "
+                              "are the dataset paths (<subject>/<action>/<name>/data)" % path)
+        src = h5py.File(path, "r")
+
+        def read(rel):
+            return np.array(src[rel]) if rel in src else None
+    try:
+        data = []
+        for key, size in zip(order_keys, sizes):
+            subject, action, name = key[0], key[1], key[2]
+            rel = "%s/%s/%s/data" % (subject, action, str(name).replace(".h5", ""))
+            outs = read(rel)
+            if outs is None:
+                raise ValueError("load_effnet_outputs: no dataset %s for key %s in %s" % (rel, (subject, action, name), path))
+            if outs.ndim != 2 or outs.shape[0] < size:
+                raise ValueError("load_effnet_outputs: dataset %s of key %s has shape %s, fewer than %d rows"
+                                 % (rel, (subject, action, name), tuple(outs.shape), size))
+            data.append(outs[:size].astype(np.float32, copy=False))
+    finally:
+        src.close()
+    if not data:
+        raise ValueError("load_effnet_outputs: no keys")
+    return np.concatenate(data, axis=0)

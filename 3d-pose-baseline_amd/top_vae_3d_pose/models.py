@@ -156,6 +156,49 @@ class VAE(object):
             t = t.to(device=self.device, dtype=torch.float32).contiguous()
         return t
 
+    def _cat(self, segs):
+        """A list of segments -- each a tensor [B, w] or a (table [rows, w], idx int64 [B]) pair -- as
+        the library's p3d_vae_cat; returns (struct, B, the tensors it points into).  Nothing is
+        copied: every segment must already be a contiguous float32 tensor on the model's device."""
+        torch = self.torch
+        if not 1 <= len(segs) <= 4:
+            raise ValueError("vae input: 1 to 4 segments, got %d" % len(segs))
+        cat, keep, B, total = _p3d.P3DVaeCat(), [], None, 0
+        cat.n = len(segs)
+        for s, seg in enumerate(segs):
+            table, idx = seg if isinstance(seg, (tuple, list)) else (seg, None)
+            if not isinstance(table, torch.Tensor) or table.dim() != 2:
+                raise ValueError("vae input: segment %d must be a tensor [rows, width]" % s)
+            if table.device != self.device or table.dtype != torch.float32 or not table.is_contiguous():
+                raise ValueError("vae input: segment %d must be a contiguous float32 tensor on %s (got %s on %s)"
+                                 % (s, self.device, table.dtype, table.device))
+            rows, w = int(table.shape[0]), int(table.shape[1])
+            if w < 8 or w % 8 != 0:
+                raise ValueError("vae input: segment %d has width %d, not a multiple of 8" % (s, w))
+            if rows < 1:
+                raise ValueError("vae input: segment %d has no rows" % s)
+            if idx is not None:
+                if (not isinstance(idx, torch.Tensor) or idx.dim() != 1 or idx.dtype != torch.int64
+                        or idx.device != self.device or not idx.is_contiguous()):
+                    raise ValueError("vae input: the index of segment %d must be a contiguous int64 vector on %s"
+                                     % (s, self.device))
+                n = int(idx.shape[0])
+            else:
+                n = rows
+            if B is None:
+                B = n
+            elif n != B:
+                raise ValueError("vae input: segment %d gives %d rows, segment 0 gives %d" % (s, n, B))
+            cat.p[s], cat.w[s], cat.idx[s], cat.rows[s] = ptr(table), w, ptr(idx) or None, rows
+            keep += [table, idx]
+            total += w
+        if total != self.input_size:
+            raise ValueError("vae input: the segments' widths sum to %d, the filter takes %d" % (total, self.input_size))
+        if B < 1:
+            raise ValueError("vae input: no rows")
+        check(lib().p3d_vae_cat_check(ctypes.byref(cat), self.input_size, B), "p3d_vae_cat_check")
+        return cat, B, keep
+
     def _factors(self, factors):
         return (ctypes.c_float * 3)(*[float(f) for f in factors])
 
@@ -164,8 +207,12 @@ class VAE(object):
         """One k_vae_fwd launch; returns a dict with the tensors named in `want` out of 'y',
         'mean', 'log_var', 'z' and, with a target, 'row_terms' [B, 3]."""
         torch = self.torch
-        x = self._dev(x, self.input_size, "vae input")
-        B = x.shape[0]
+        cat = None
+        if isinstance(x, list):     # [seg, ...]: the concatenation is formed inside the kernels
+            cat, B, _keep = self._cat(x)
+        else:
+            x = self._dev(x, self.input_size, "vae input")
+            B = x.shape[0]
         eps = None if eps is None else self._dev(eps, self.latent_dim, "eps")
         if eps is not None and eps.shape[0] != B:
             raise ValueError("eps: expected %d rows, got %d" % (B, eps.shape[0]))
@@ -176,22 +223,30 @@ class VAE(object):
         out = {k: torch.empty((B, widths[k]), dtype=torch.float32, device=self.device) for k in want if k in widths}
         if target is not None:
             out["row_terms"] = torch.empty((B, 3), dtype=torch.float32, device=self.device)
-        check(lib().p3d_vae_forward(self._h, ptr(x), B, ptr(eps), int(ctr), ptr(out.get("y")), ptr(out.get("mean")),
-                                    ptr(out.get("log_var")), ptr(out.get("z")), ptr(target), ptr(out.get("row_terms")),
-                                    self.stream()), "p3d_vae_forward")
+        fn, what, xin = ((lib().p3d_vae_forward, "p3d_vae_forward", ptr(x)) if cat is None else
+                         (lib().p3d_vae_forward_cat, "p3d_vae_forward_cat", ctypes.byref(cat)))
+        check(fn(self._h, xin, B, ptr(eps), int(ctr), ptr(out.get("y")), ptr(out.get("mean")),
+                 ptr(out.get("log_var")), ptr(out.get("z")), ptr(target), ptr(out.get("row_terms")),
+                 self.stream()), what)
         return out
 
     def _step(self, fn, what, x, t, eps, middle, loss_out=None):
-        """`middle`: the arguments between eps and loss3_dev (ctr, factors | factors, lr)."""
-        x = self._dev(x, self.input_size, "vae input")
+        """`middle`: the arguments between eps and loss3_dev (ctr, factors | factors, lr).  A list in
+        place of x (segments, see _cat) goes to the call's _cat twin."""
+        if isinstance(x, list):
+            cat, B, _keep = self._cat(x)
+            fn, what, xin = getattr(lib(), what + "_cat"), what + "_cat", ctypes.byref(cat)
+        else:
+            x = self._dev(x, self.input_size, "vae input")
+            B, xin = x.shape[0], ptr(x)
         t = self._dev(t, self.human_3d_size, "target")
-        if t.shape[0] != x.shape[0]:
-            raise ValueError("target: expected %d rows, got %d" % (x.shape[0], t.shape[0]))
+        if t.shape[0] != B:
+            raise ValueError("target: expected %d rows, got %d" % (B, t.shape[0]))
         eps = None if eps is None else self._dev(eps, self.latent_dim, "eps")
-        if eps is not None and eps.shape[0] != x.shape[0]:
-            raise ValueError("eps: expected %d rows, got %d" % (x.shape[0], eps.shape[0]))
+        if eps is not None and eps.shape[0] != B:
+            raise ValueError("eps: expected %d rows, got %d" % (B, eps.shape[0]))
         loss = self._loss if loss_out is None else loss_out
-        check(fn(self._h, ptr(x), ptr(t), x.shape[0], ptr(eps), *middle, ptr(loss), self.stream()), what)
+        check(fn(self._h, xin, ptr(t), B, ptr(eps), *middle, ptr(loss), self.stream()), what)
         return loss
 
     def loss_device(self, x, t, factors, eps=None, ctr=0, loss_out=None):
@@ -218,6 +273,9 @@ class VAE(object):
 
     # ------------------------------------------------------------------ the recurrence over sequences
     def _seq_len(self):
+        if self.input_size > 256:
+            raise ValueError("filter_sequences: a wide filter (input_size %d > 256) has no sequence form"
+                             % self.input_size)
         if self.input_size % self.human_3d_size != 0 or not 1 <= self.input_size // self.human_3d_size <= 5:
             raise ValueError("filter_sequences: input_size %d is not 1 .. 5 times human_3d_size %d"
                              % (self.input_size, self.human_3d_size))
@@ -353,9 +411,10 @@ class Pose3DVae(object):
     def __init__(self, latent_dim, enc_dim, dec_dim, use_effnet_ouptut=False, use_2d=False, pred_bones=False, *,
                  pose3d=None, max_batch=4096, seed=None):
         if use_2d:
-            raise NotImplementedError("Pose3DVae(use_2d=True) (the 80-input filter over [x2d, out_3d]) is not built")
+            raise NotImplementedError("Pose3DVae(use_2d=True) is served by Pose3DVaeCat (the filter over [x2d, out_3d])")
         if use_effnet_ouptut:
-            raise NotImplementedError("Pose3DVae(use_effnet_ouptut=True) (EfficientNet features) is not built")
+            raise NotImplementedError("Pose3DVae(use_effnet_ouptut=True) is served by Pose3DVaeCat (precomputed "
+                                      "EfficientNet features as a segment of the filter's input)")
         if pred_bones:
             raise NotImplementedError("Pose3DVae(pred_bones=True) (VAEBones) is not built")
         if pose3d is None:
@@ -371,9 +430,74 @@ class Pose3DVae(object):
 
     def __call__(self, inputs, effnet_output=None, training=False, eps=None):
         if effnet_output is not None:
-            raise NotImplementedError("Pose3DVae: effnet_output is not built")
+            raise NotImplementedError("Pose3DVae: effnet_output is taken by Pose3DVaeCat")
         out_3d = self.pose3d.serve_device(inputs)      # raises ValueError on a bad shape
         return out_3d, self.vae(out_3d, training=training, eps=eps)
+
+    def save_weights(self, path):
+        self.vae.save_weights(path)
+
+    def load_weights(self, path):
+        self.vae.load_weights(path)
+
+    def close(self):
+        self.vae.close()
+
+
+class Pose3DVaeCat(object):
+    """The frozen lifter + the VAE filter over a concatenated input (models.py:485-540 built with
+    use_2d and / or use_effnet_ouptut): call(x2d, effnet_output) -> (out_3d, out_vae).  The filter's
+    input is [inputs, out_3d] (use_2d), then effnet_output (models.py:532-536); the concatenation is
+    formed inside the filter's kernels.  effnet_output is a [B, effnet_size] tensor or a (table,
+    idx) pair: row r reads table[idx[r]] -- the precomputed features of data_handler.py:325-340."""
+
+    def __init__(self, latent_dim, enc_dim, dec_dim, use_effnet_ouptut=False, use_2d=False, pred_bones=False, *,
+                 pose3d=None, effnet_size=1280, max_batch=4096, seed=None):
+        if pred_bones:
+            raise NotImplementedError("Pose3DVaeCat(pred_bones=True) (VAEBones) is not built")
+        if pose3d is None:
+            raise ValueError("Pose3DVaeCat needs the lifter: pass pose3d=LinearModel(...)")
+        if pose3d.output_size != HUMAN_3D_SIZE:
+            raise ValueError("Pose3DVaeCat: the lifter must predict %d outputs, not %d"
+                             % (HUMAN_3D_SIZE, pose3d.output_size))
+        self.use_2d, self.use_effnet_ouptut, self.pred_bones = bool(use_2d), bool(use_effnet_ouptut), False
+        self.human_3d_size, self.human_2d_size = HUMAN_3D_SIZE, HUMAN_2D_SIZE
+        self.effnet_size = int(effnet_size)
+        self.pose3d = pose3d
+        self.input_size = (HUMAN_2D_SIZE if use_2d else 0) + HUMAN_3D_SIZE + (self.effnet_size if use_effnet_ouptut else 0)
+        self.vae = VAE(self.input_size, latent_dim, enc_dim, dec_dim, max_batch=max_batch, seed=seed,
+                       device=pose3d.device.index)
+
+    def segments(self, inputs, out_3d, effnet_output=None):
+        """The filter's input as the list of segments VAE's device entry points take."""
+        torch = self.vae.torch
+        B = int(out_3d.shape[0])
+        segs = [inputs, out_3d] if self.use_2d else [out_3d]
+        if self.use_effnet_ouptut:
+            if effnet_output is None:
+                raise ValueError("Pose3DVaeCat: this model was built with use_effnet_ouptut: pass effnet_output")
+            table, idx = effnet_output if isinstance(effnet_output, (tuple, list)) else (effnet_output, None)
+            if not isinstance(table, torch.Tensor):
+                table = torch.from_numpy(np.array(table, dtype=np.float32, order="C")).to(self.vae.device)
+            if table.dim() != 2 or table.shape[1] != self.effnet_size:
+                raise ValueError("effnet_output: expected shape [None, %d], got %s" % (self.effnet_size, tuple(table.shape)))
+            n = int(table.shape[0]) if idx is None else int(idx.shape[0])
+            if n != B:
+                raise ValueError("effnet_output: expected %d rows, got %d" % (B, n))
+            segs.append(table if idx is None else (table, idx))
+        elif effnet_output is not None:
+            raise ValueError("Pose3DVaeCat: effnet_output given to a model built without use_effnet_ouptut")
+        return segs
+
+    def __call__(self, inputs, effnet_output=None, training=False, eps=None):
+        torch = self.vae.torch
+        if not isinstance(inputs, torch.Tensor):
+            inputs = torch.from_numpy(np.array(inputs, dtype=np.float32, order="C"))
+        inputs = inputs.to(device=self.vae.device, dtype=torch.float32).contiguous()
+        out_3d = self.pose3d.serve_device(inputs)      # raises ValueError on a bad shape
+        self.vae._calls += 1
+        y = self.vae.forward_device(self.segments(inputs, out_3d, effnet_output), eps=eps, ctr=self.vae._calls)["y"]
+        return out_3d, y
 
     def save_weights(self, path):
         self.vae.save_weights(path)

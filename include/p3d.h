@@ -501,10 +501,18 @@ uint32_t p3d_crc32c(const void* data, int64_t n, uint32_t crc);
  * ------------------------------------------------------------------------------------------ */
 typedef struct p3d_vae p3d_vae;
 
-/* keras.Model construction of models.py:25-52.  in <= 256; 1-4 hidden layers each side, widths
+/* keras.Model construction of models.py:25-52.  in <= 2048; 1-4 hidden layers each side, widths
  * <= 256; latent <= 64; out <= 64; every width a multiple of 8; max_batch <= 2^20 bounds the
  * rows of the loss / gradient / training calls; the parameters and the working space of four
  * 16-row tiles must fit one workgroup's LDS.  Anything else: P3D_ERR_ARG and a message.
+ * in > 256 is the WIDE form (csrc/p3d_vae_wide.h; models.py:485-540 with use_2d and
+ * use_effnet_ouptut: in = 32 + 48 + 1280): layer 0's kernel [in, enc_dims[0]] and bias stay in
+ * their master buffer and are read through L2, every other layer keeps the packed LDS copy, and a
+ * call is three launches ordered by the stream (layer 0 forward; the filter behind it; layer 0's
+ * weight gradient and optimizer).  The parameter table, the names and the flat buffers are laid
+ * out alike in both forms.  The weight gradient of layer 0 is one accumulator chain over the B
+ * rows in row order: no per-block partial of it exists, and every gradient sum stays associated
+ * by the row index alone.  p3d_vae_seq_filter refuses a wide filter.
  * Parameters start at zero (the host writes Glorot kernels through the parameter table);
  * `seed` keys the eps stream. */
 int p3d_vae_create(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent, int32_t n_dec,
@@ -512,7 +520,8 @@ int p3d_vae_create(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t l
 int p3d_vae_destroy(p3d_vae* v);
 /* Bytes of LDS a workgroup of this shape's kernels uses (the packed parameters + four 16-row
  * tiles of activations), as p3d_vae_create lays them out; 0 for a shape it refuses for another
- * reason.  Host only. */
+ * reason.  A wide shape answers what its largest workgroup uses: the filter behind layer 0 (the
+ * layer-0 kernels use no LDS).  Host only. */
 int64_t p3d_vae_lds_bytes(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent, int32_t n_dec,
                           const int32_t* dec_dims, int32_t out);
 
@@ -568,8 +577,38 @@ int p3d_vae_set_step(p3d_vae* v, int64_t step, float beta1_power, float beta2_po
 /* Rows row0 .. row0 + B - 1 of the eps stream (tf.random.normal of models.py:70) as
  * p3d_vae_forward draws them: out [B, latent], latent a multiple of 4. */
 int p3d_vae_eps(uint64_t seed, uint64_t ctr, int64_t row0, int64_t B, int32_t latent, float* out, void* stream);
-/* Bytes of the library-owned workspace a gradient over B rows uses (per-block partials). */
+/* Bytes of the library-owned workspace a gradient over B rows uses (per-block partials; a wide
+ * filter: the partials of the layers behind layer 0, plus h0 and dz0, 2 B enc_dims[0] floats). */
 int64_t p3d_vae_workspace(const p3d_vae* v, int64_t B);
+
+/* The input as a concatenation [seg 0 | seg 1 | ...] of up to four column segments, each a
+ * resident table read row by row or through an index vector -- the reference's
+ * tf.concat([inputs, out_3d, effnet_out], axis=1) (models.py:532-536) with the feature rows picked
+ * by the epoch's permutation, formed inside the kernels instead of by a concat and a gather per
+ * step.  The struct is read at the call.  The device clamps every index into [0, rows - 1]. */
+typedef struct {
+  int32_t n;                 /* 1 .. 4 segments, widths multiples of 8 summing to `in`            */
+  const float* p[4];         /* device, 16-byte aligned; segment s is [rows_s, w[s]] row-major    */
+  int32_t w[4];
+  const int64_t* idx[4];     /* device [B] or null: row r of the input reads row idx[s][r]        */
+  int64_t rows[4];           /* rows of segment s's table; idx values are clamped into it         */
+} p3d_vae_cat;
+/* The struct's checks against a filter of `in` inputs and a call of B rows (P3D_ERR_ARG and a
+ * message): n, the widths and their sum, null or misaligned pointers, rows >= 1, and rows >= B for
+ * a segment without an index.  Host only. */
+int p3d_vae_cat_check(const p3d_vae_cat* cat, int32_t in, int64_t B);
+/* p3d_vae_forward / _loss / _grad / _train_step with the segments in place of x: the bits of the
+ * plain call on the materialised concatenation.  They serve narrow filters too ([x2d | out_3d],
+ * in = 80, is the reference's use_2d alone).  On a wide filter the plain calls are the
+ * one-segment, no-index case of the same kernels. */
+int p3d_vae_forward_cat(p3d_vae* v, const p3d_vae_cat* cat, int64_t B, const float* eps, uint64_t ctr, float* y,
+                        float* mean, float* log_var, float* z, const float* target, float* row_terms, void* stream);
+int p3d_vae_loss_cat(p3d_vae* v, const p3d_vae_cat* cat, const float* t, int64_t B, const float* eps, uint64_t ctr,
+                     const float* factors, float* loss3_dev, void* stream);
+int p3d_vae_grad_cat(p3d_vae* v, const p3d_vae_cat* cat, const float* t, int64_t B, const float* eps, uint64_t ctr,
+                     const float* factors, float* loss3_dev, void* stream);
+int p3d_vae_train_step_cat(p3d_vae* v, const p3d_vae_cat* cat, const float* t, int64_t B, const float* eps,
+                           const float* factors, float lr, float* loss3_dev, void* stream);
 
 /* The temporal filter (in == seq_len * out, 1 <= seq_len <= 5) run as the reference's recurrence
  * (3d_pose_vae_filter_kin.py evaluate()) over S whole sequences in ONE launch:
