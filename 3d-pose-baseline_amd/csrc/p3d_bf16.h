@@ -179,7 +179,7 @@ __global__ __launch_bounds__(256) void k_gemm_bf16(GemmBf16Args p) {
       const int n = col + e;
       float z = et[rl * 132 + cl + e] + p.epi.bias[n];
       float y = p.epi.inv ? z * p.epi.inv[n] + p.epi.shift[n] : z;
-      if (p.epi.relu) y = fmaxf(y, 0.0f);
+      if (p.epi.relu) y = p3d_relu(y);
       if (p.res) y += p3d_bf2f(rv[e]);
       o[e] = p3d_f2bf(y);
     }
@@ -337,7 +337,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemm_bf16p(GemmBf16Args p) {
       const int n = col + e;
       float z = et[rl * 132 + cl + e] + p.epi.bias[n];
       float y = p.epi.inv ? z * p.epi.inv[n] + p.epi.shift[n] : z;
-      if (p.epi.relu) y = fmaxf(y, 0.0f);
+      if (p.epi.relu) y = p3d_relu(y);
       if (p.res) y += p3d_bf2f(rv[e]);
       o[e] = p3d_f2bf(y);
     }

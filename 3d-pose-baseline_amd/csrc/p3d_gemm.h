@@ -165,7 +165,7 @@ __global__ __launch_bounds__(256) void k_gemm_f32(GemmF32Args p) {
       for (int e = 0; e < 4; ++e) {
         const float z = (p.wsq ? acc[r][c][e] / mx : acc[r][c][e]) + b4[e];
         float y = p.bn ? z * inv[e] + shift[e] : z;
-        if (p.relu) y = fmaxf(y, 0.0f);
+        if (p.relu) y = p3d_relu(y);
         if (p.keep < 1.0f) y = (y / p.keep) * p3d_dropout_mask(p.keep, u[e]);
         if (p.res) y += rv[e];
         o[e] = y;

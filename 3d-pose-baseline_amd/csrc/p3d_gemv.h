@@ -130,7 +130,7 @@ __device__ __forceinline__ float p3d_gemv_epi(const GemvArgs& p, const GemvEpi& 
     const float shift = e.bet - e.mmu * inv;
     y = z * inv + shift;
   }
-  if (p.relu) y = fmaxf(y, 0.0f);
+  if (p.relu) y = p3d_relu(y);
   if (p.keep < 1.0f) y = (y / p.keep) * p3d_dropout_mask(p.keep, p3d_uniform(p.seed, e.ctr, p.site, p.row_off + row, cc));
   if (p.res) y += e.rv;
   return y;

@@ -35,6 +35,14 @@ __device__ __forceinline__ f32x4 p3d_ld_sc1(__amdgpu_buffer_rsrc_t r, int byte_o
   return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 16));
 }
 
+// ReLU that propagates NaN, as np.maximum / tf.nn.relu do in the oracles: IEEE-754-2019
+// `maximum`, one v_maximum3_f32 on gfx950.  fmaxf is `maxNum` (v_max_f32), which returns the
+// operand that is not a NaN and would turn a poisoned activation into 0; a non-finite input
+// row must leave every kernel as a NaN row ("Non-finite input").  The remaining
+// fmaxf calls are deliberate: the max-norm clamp fmaxf(sqrtf(wsq), 1.0f) and the RNG floor
+// fmaxf(u1, 1e-7f) act on weights and on random bits, never on data.
+__device__ __forceinline__ float p3d_relu(float v) { return __builtin_elementwise_maximum(v, 0.0f); }
+
 // float offset of element (r, c) in a packed matrix with ng = C/16 column groups
 __device__ __host__ __forceinline__ int64_t p3d_pk(int r, int c, int ng) {
   return (((int64_t)(r >> 4) * ng + (c >> 4)) << 8) + (((r & 15) + ((c & 15) >> 2) * 16) << 2) + (c & 3);

@@ -430,7 +430,7 @@ __global__ __launch_bounds__(64 * WK) void k_fwd(FwdArgs p) {
       if (row >= p.M) continue;
       if (p.z_save) p.z_save[p3d_pk(row, col, ngN)] = z[s][r];
       float y = p.bn == 4 ? p3d_bn_y(z[s][r], inv, shift) : p.bn ? z[s][r] * inv + shift : z[s][r];
-      if (p.relu) y = fmaxf(y, 0.0f);
+      if (p.relu) y = p3d_relu(y);
       if (p.keep < 1.0f) y = (y / p.keep) * p3d_dropout_mask(p.keep, uu[s][r]);
       if (p.res) y += rv[s][r];
       if (YPK) p.Y[p3d_pk(row, col, ngN)] = y;
@@ -557,7 +557,7 @@ __global__ __launch_bounds__(64) void k_bn_fwd(BnFwdArgs p) {
     float inv, shift;
     p3d_bn_affine(mean, var, p.eps, g4[e], b4[e], inv, shift);
     float y = p3d_bn_y(z4[e], inv, shift);
-    if (p.relu) y = fmaxf(y, 0.0f);
+    if (p.relu) y = p3d_relu(y);
     if (p.keep < 1.0f) y = (y / p.keep) * p3d_dropout_mask(p.keep, u[e]);
     if (p.res) y += r4[e];
     o[e] = row < p.M ? y : 0.0f;
@@ -760,7 +760,7 @@ __device__ __forceinline__ void p3d_dgrad_body(const BwdArgs& p, int bx, int by,
       float gg = g[s][r];
       if (p.keep < 1.0f) gg = (gg * p3d_dropout_mask(p.keep, uu[s][r])) / p.keep;
       const float a = p.bn ? p3d_bn_y(zz[s][r], inv, shift) : zz[s][r];   // the forward's own rounding
-      if (p.relu && !(a > 0.0f)) gg = 0.0f;
+      if (p.relu) gg *= a > 0.0f ? 1.0f : 0.0f;   // g * (a > 0), a product as in TF's ReluGrad: a NaN gradient stays NaN
       if (!ok) gg = 0.0f;
       g[s][r] = gg;
       const float x = (zz[s][r] - mean) * rstd;

@@ -335,9 +335,9 @@ __device__ __forceinline__ f32x4 p3d_epi_apply(const ServeEpi& ep, f32x4 acc, bo
     if (bn) {
       const float inv = (1.0f / sqrtf(ep.va[e] + eps)) * ep.g[e];
       const float shift = ep.be[e] - ep.mu[e] * inv;
-      o[e] = fmaxf(z * inv + shift, 0.0f);
+      o[e] = p3d_relu(z * inv + shift);
     } else {
-      o[e] = fmaxf(z, 0.0f);
+      o[e] = p3d_relu(z);
     }
   }
   return o;
@@ -777,7 +777,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const float z = (wsq_any ? acc[k] / mx : acc[k]) + b4[k];
-      o[k] = fmaxf(p.bn ? z * inv4[k] + sh4[k] : z, 0.0f);
+      o[k] = p3d_relu(p.bn ? z * inv4[k] + sh4[k] : z);
     }
     return o;
   };

@@ -292,7 +292,7 @@
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const float z = acc[k] + b4[k];
-      o[k] = fmaxf(p.bn ? z * inv4[k] + sh4[k] : z, 0.0f);
+      o[k] = p3d_relu(p.bn ? z * inv4[k] + sh4[k] : z);
     }
     return o;
   };

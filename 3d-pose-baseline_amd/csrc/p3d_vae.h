@@ -186,7 +186,7 @@ __device__ __forceinline__ void vae_layer_fwd(const VaeLayer& L, const float* ar
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       float v = acc[r] + b;
-      if (relu) v = fmaxf(v, 0.0f);
+      if (relu) v = p3d_relu(v);
       out[(4 * q + r) * ldo + 16 * ct + i] = v;
     }
   }
@@ -211,7 +211,7 @@ __device__ __forceinline__ void vae_layer_fwd_cat(const VaeLayer& L, const VaeCa
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       float v = acc[r] + b;
-      if (relu) v = fmaxf(v, 0.0f);
+      if (relu) v = p3d_relu(v);
       out[(4 * q + r) * ldo + 16 * ct + i] = v;
     }
   }
@@ -363,7 +363,7 @@ __device__ __forceinline__ void vae_tile_fwd(const VaeArgs& a, const VaeDesc* d,
         const float tt = (ta[a4][0] * tb[0] + ta[a4][1] * tb[1]) + ta[a4][2] * tb[2];
         const float phi = pp - tt;
         s += fabsf(phi);
-        const float sg = phi > 0.0f ? 1.0f : (phi < 0.0f ? -1.0f : 0.0f);   // tf.abs gradient: sign, sign(0) = 0
+        const float sg = phi > 0.0f ? 1.0f : (phi < 0.0f ? -1.0f : (phi == 0.0f ? 0.0f : phi));   // tf.abs gradient: sign, sign(0) = 0, sign(NaN) = NaN
 #pragma unroll
         for (int c = 0; c < 3; ++c) dB[a4][c] += sg * pb[c];
       }
@@ -624,7 +624,7 @@ __device__ __forceinline__ void vae_step_body(const VaeArgs& a) {
               for (int r = 0; r < 4; ++r) {
                 const int row = 4 * q + r;
                 const float av = ab[row * L.lda + kc];
-                ab[row * L.lda + kc] = av > 0.0f ? acc[r] : 0.0f;
+                ab[row * L.lda + kc] = acc[r] * (av > 0.0f ? 1.0f : 0.0f);   // a product (ReluGrad): a NaN gradient stays NaN
               }
             }
           }

@@ -97,7 +97,7 @@ __device__ __forceinline__ void vae_seq_layer(const VaeLayer& L, const float* ar
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       float v = acc[r] + b;
-      if (relu) v = fmaxf(v, 0.0f);
+      if (relu) v = p3d_relu(v);
       out[(4 * q + r) * ldo + 16 * ct + i] = v;
     }
   }

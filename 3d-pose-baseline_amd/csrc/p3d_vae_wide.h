@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void k_vae_wide_fwd(VaeWideArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int64_t orow = rt * 16 + 4 * q + r;
-        if (orow < a.B) a.h0[orow * n0 + n] = fmaxf(acc[r] + bias, 0.0f);
+        if (orow < a.B) a.h0[orow * n0 + n] = p3d_relu(acc[r] + bias);
       }
     }
   }
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(256) void k_vae_wide_wgrad_adam(VaeWideArgs a) {
         }
         x = xp[xr * w];
       }
-      const float z = hp[rr * n0] > 0.0f ? zp[rr * n0] : 0.0f;
+      const float z = zp[rr * n0] * (hp[rr * n0] > 0.0f ? 1.0f : 0.0f);   // a product (ReluGrad): a NaN gradient stays NaN
       av[s] = valid && (ink || bias) ? x : 0.0f;
       bv[s] = valid && inn ? z : 0.0f;
     }

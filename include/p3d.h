@@ -157,7 +157,10 @@ int p3d_serve_mse_sync(p3d_model* m, const float* x, int64_t B, float* y, const 
 /* 0 if every p3d_serve launch so far completed its synchronisation (synchronises the device,
  * then reads the kernels' pinned error word).  After a failure p3d_serve refuses new launches
  * (P3D_ERR_HIP) until this call reports it once; the failed launch's rows hold NaN, never
- * unwritten or stale values.  k_serve6 launches pick their sync-word bank on the device, so a
+ * unwritten or stale values.  NaN rows alone do not mean failure: a non-finite input row gives a
+ * NaN output row (and a NaN loss) on every path, as in the reference, with the error words clean
+ * -- NaN rows with a set error word are a failed launch, NaN rows without one are bad input.
+ * k_serve6 launches pick their sync-word bank on the device, so a
  * captured p3d_serve replays correctly (its epilogue-constant table is re-formed in the graph). */
 int p3d_serve_check(p3d_model* m);
 

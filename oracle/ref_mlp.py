@@ -491,10 +491,13 @@ def eval_step(state: State, x, t, dt=np.float64):
 
 
 def bf16_round(a):
-    """Round to the nearest bf16 (ties to even), returned as float32."""
-    u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    """Round to the nearest bf16 (ties to even), returned as float32.  A NaN stays a NaN (the
+    integer rounding alone would carry a NaN whose payload sits in the low 16 bits into Inf or
+    -0); +-Inf stay as they are."""
+    f = np.ascontiguousarray(a, dtype=np.float32)
+    u = f.view(np.uint32).astype(np.uint64)
     r = ((u + np.uint64(0x7FFF) + ((u >> np.uint64(16)) & np.uint64(1))) >> np.uint64(16)) << np.uint64(16)
-    return r.astype(np.uint32).view(np.float32)
+    return np.where(np.isnan(f), np.float32(np.nan), r.astype(np.uint32).view(np.float32))
 
 
 def forward_bf16(state: State, x, acc=np.float64):
