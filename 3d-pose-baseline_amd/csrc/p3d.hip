@@ -922,7 +922,9 @@ static int launch_fwd(p3d_model* m, const FwdArgs& a, int kind, bool whole_batch
   }
   static const char* tags[2][3] = {{"fwd_in", "fwd_hidden", "fwd_out"},
                                    {"fwd_in_train", "fwd_hidden_train", "fwd_out_train"}};
-  ProfScope ps(m, tags[whole_batch ? 1 : 0][kind]);
+  // (the output layer with the fused MSE -- a training step that does not take k_out_part -- is
+  // told apart from the inference output layer in the profile)
+  ProfScope ps(m, tags[whole_batch || (kind == 2 && a.tgt) ? 1 : 0][kind]);
   int wk = whole_batch ? m->train_wk : m->infer_wk;
   if (!whole_batch && kind == 0 && m->in_wk) wk = m->in_wk;
   // training output layer (fused MSE, 12 workgroups at B = 64): the 8-deep ring (all of a wave's
@@ -1627,6 +1629,10 @@ extern "C" int p3d_backward(p3d_model* m, const float* dy, int64_t B, void* stre
     wa.M = (int)B; wa.K = ly.K; wa.N = ly.N;
     wa.dW = grads + ly.w; wa.db = grads + ly.b;
     const bool fuse = m->fuse_adam != nullptr;
+    // the per-layer k_wgrad of the output layer reads dy: where this layer's data-gradient launch
+    // forms it (from k_out_part's partials) the weight gradient follows that launch.  (The
+    // one-launch forms run after the loop, the fused step's after each data gradient anyway.)
+    const bool defer_out = !fuse && !multi && opart && l == nl - 1;
     if (fuse) {
       // single-GPU train step: Adam where the gradient is formed.  W(l) is read by dgrad(l),
       // so dW + Adam(l) runs after it; the previous layer's gamma/beta (read by dgrad(l) and
@@ -1637,7 +1643,7 @@ extern "C" int p3d_backward(p3d_model* m, const float* dy, int64_t B, void* stre
       if (l >= 1 && m->layers[l - 1].bn) {
         wa.bn_adam = 1; wa.gflat = grads; wa.goff = m->layers[l - 1].gamma; wa.btoff = m->layers[l - 1].beta;
       }
-    } else {
+    } else if (!defer_out) {
       int rc = emit(wa);
       if (!rc) rc = flush_bucket(l);
       if (rc) return rc;
@@ -1735,7 +1741,7 @@ extern "C" int p3d_backward(p3d_model* m, const float* dy, int64_t B, void* stre
       LAUNCH_CHECK("k_dgrad");
     }
     if (a.draw) { dres_next = a.draw; dsel ^= 1; }
-    if (fuse) {
+    if (fuse || defer_out) {
       int rc = emit(wa);
       if (rc) return rc;
     }
