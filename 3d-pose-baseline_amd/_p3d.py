@@ -165,6 +165,12 @@ SIGNATURES = [
     ("p3d_vae_seq_set_form", c_int32, [c_void_p, c_int32]),
     ("p3d_vae_seq_lds_bytes", c_int64, [c_int32, c_int32, POINTER(c_int32), c_int32, c_int32, POINTER(c_int32),
                                         c_int32, c_int32]),
+    ("p3d_vae_create_bones", c_int32, [c_int32, c_int32, POINTER(c_int32), c_int32, c_int32, POINTER(c_int32),
+                                       c_int32, c_uint64, POINTER(c_void_p)]),
+    ("p3d_vae_bones_lds_bytes", c_int64, [c_int32, c_int32, POINTER(c_int32), c_int32, c_int32, POINTER(c_int32)]),
+    ("p3d_vae_kind", c_int32, [c_void_p]),
+    ("p3d_bones_from_joints", c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    ("p3d_bones_to_joints", c_int32, [c_void_p, c_int64, c_void_p, c_void_p]),
 ]
 
 

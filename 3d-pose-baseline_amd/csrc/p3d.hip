@@ -40,6 +40,7 @@
 
 #include "p3d_layers.h"
 #include "p3d_vae.h"
+#include "p3d_bones.h"
 #include "p3d_vae_seq.h"
 #include "p3d_vae_wide.h"
 
@@ -2614,6 +2615,7 @@ struct p3d_vae {
   VaeDesc desc{};
   std::vector<std::string> names;       // Keras order; tensor i is desc.T[i]
   int max_batch = 0, form = 0, cus = 0;
+  int kind = P3D_VAE_KIND_ELBO;         // the loss kind (and, bones, the decoder's mag1 / {mag2, cos2} end)
   uint64_t seed = 0;
   size_t lds = 0;                       // dynamic LDS bytes of k_vae_fwd / k_vae_step
   int64_t ws_floats = 0;
@@ -2641,9 +2643,11 @@ int ceil16(int n) { return (n + 15) / 16 * 16; }
 // The layout of a filter (host only): layers, the packed copy, a wave's LDS area, the master
 // tensors.  wpad = 4 staggers the packed rows over the LDS banks for the data-gradient reads;
 // 0 is the fall-back when that does not fit; stage_x keeps the 16-row input tile in LDS too (else
-// layer 0 reads x from global memory).  Returns the dynamic LDS bytes.
-size_t vae_layout(VaeDesc& d, std::vector<std::string>& names, int in, int n_enc, const int32_t* enc, int latent,
-                  int n_dec, const int32_t* dec, int out, int wpad, int stage_x) {
+// layer 0 reads x from global memory).  kind = bones: behind the dec_dim layers come mag1 (16,
+// ReLU) and one packed output layer [16, 64] = {mag2 | cos2} (models.py:555-566; cos1 is not
+// reachable from the decoder's outputs and is not part of the model).  Returns the dynamic LDS bytes.
+size_t vae_layout(VaeDesc& d, std::vector<std::string>& names, int kind, int in, int n_enc, const int32_t* enc,
+                  int latent, int n_dec, const int32_t* dec, int out, int wpad, int stage_x) {
   d = VaeDesc{};
   names.clear();
   d.in = in; d.latent = latent; d.out = out;
@@ -2680,18 +2684,27 @@ size_t vae_layout(VaeDesc& d, std::vector<std::string>& names, int in, int n_enc
     L.fb2 = tensor("log_varianze/bias", 1, latent, L.bpk + latent, L.Np);
     prev = latent;
   }
-  for (int e = 0; e <= n_dec; ++e) {
-    const int N = e < n_dec ? dec[e] : out;
-    VaeLayer& L = layer(prev, N, e < n_dec);
-    const std::string s = e < n_dec ? "dec_f_" + std::to_string(N) : std::string("dec_f_out");
+  const bool bones = kind == P3D_VAE_KIND_BONES;
+  for (int e = 0; e <= n_dec; ++e) {   // (behind the dec_dim layers: dec_f_out, or the bones filter's mag1)
+    const int N = e < n_dec ? dec[e] : (bones ? 16 : out);
+    VaeLayer& L = layer(prev, N, e < n_dec || bones);
+    const std::string s = e < n_dec ? "dec_f_" + std::to_string(N) : std::string(bones ? "mag1" : "dec_f_out");
     L.fw = tensor(s + "/kernel", L.K, L.N, L.wpk, L.ld);
     L.fb = tensor(s + "/bias", 1, L.N, L.bpk, L.Np);
     prev = N;
   }
+  if (bones) {   // mag2 (16) and cos2 (48), both on mag1's output: one packed layer split like the head
+    VaeLayer& L = layer(prev, 64, 0);
+    L.split = 16;
+    L.fw = tensor("mag2/kernel", L.K, 16, L.wpk, L.ld);
+    L.fb = tensor("mag2/bias", 1, 16, L.bpk, L.Np);
+    L.fw2 = tensor("cos2/kernel", L.K, 48, L.wpk + 16, L.ld);
+    L.fb2 = tensor("cos2/bias", 1, 48, L.bpk + 16, L.Np);
+  }
   d.ldz = ceil16(latent) + 2; d.zbuf = act; act += 16 * d.ldz;
   d.lde = d.ldz; d.ebuf = act; act += 16 * d.lde;
   d.ldb = 50; d.bt = act;
-  if (out == 48) act += 16 * d.ldb;
+  if (out == 48 || bones) act += 16 * d.ldb;   // (bones: the 48 target cosines of the ANG term)
   d.ldx = ceil16(in) + 2; d.xbuf = -1;
   if (stage_x) { d.xbuf = act; act += 16 * d.ldx; }
   for (int l = 0; l < d.nl; ++l) {
@@ -2707,12 +2720,12 @@ size_t vae_layout(VaeDesc& d, std::vector<std::string>& names, int in, int n_enc
 }
 
 // the roomiest layout that fits one workgroup's LDS (else the last one's size, over the limit)
-size_t vae_best_layout(VaeDesc& d, std::vector<std::string>& names, int in, int n_enc, const int32_t* enc, int latent,
-                       int n_dec, const int32_t* dec, int out) {
+size_t vae_best_layout(VaeDesc& d, std::vector<std::string>& names, int kind, int in, int n_enc, const int32_t* enc,
+                       int latent, int n_dec, const int32_t* dec, int out) {
   const int tries[3][2] = {{4, 1}, {4, 0}, {0, 0}};
   size_t lds = 0;
   for (auto& t : tries) {
-    lds = vae_layout(d, names, in, n_enc, enc, latent, n_dec, dec, out, t[0], t[1]);
+    lds = vae_layout(d, names, kind, in, n_enc, enc, latent, n_dec, dec, out, t[0], t[1]);
     if (lds <= P3D_VAE_LDS_LIMIT) break;
   }
   return lds;
@@ -2721,17 +2734,17 @@ size_t vae_best_layout(VaeDesc& d, std::vector<std::string>& names, int in, int 
 // The layout of any accepted shape: narrow as vae_best_layout; wide (in > 256) the core's layout
 // with layer 0 leading the names and the parameter table.  Returns the largest workgroup's LDS
 // (the wide kernels of layer 0 use none).
-size_t vae_full_layout(VaeDesc& d, std::vector<std::string>& names, std::vector<VaeTensor>& tensors, int& P0, int in,
-                       int n_enc, const int32_t* enc, int latent, int n_dec, const int32_t* dec, int out) {
+size_t vae_full_layout(VaeDesc& d, std::vector<std::string>& names, std::vector<VaeTensor>& tensors, int& P0, int kind,
+                       int in, int n_enc, const int32_t* enc, int latent, int n_dec, const int32_t* dec, int out) {
   tensors.clear();
   P0 = 0;
   if (in <= 256) {
-    const size_t lds = vae_best_layout(d, names, in, n_enc, enc, latent, n_dec, dec, out);
+    const size_t lds = vae_best_layout(d, names, kind, in, n_enc, enc, latent, n_dec, dec, out);
     tensors.assign(d.T, d.T + d.nt);
     return lds;
   }
   std::vector<std::string> core;
-  const size_t lds = vae_best_layout(d, core, enc[0], n_enc - 1, enc + 1, latent, n_dec, dec, out);
+  const size_t lds = vae_best_layout(d, core, kind, enc[0], n_enc - 1, enc + 1, latent, n_dec, dec, out);
   P0 = (in + 1) * enc[0];
   const std::string s = "enc_h_" + std::to_string(enc[0]);
   names = {s + "/kernel", s + "/bias"};
@@ -2804,6 +2817,7 @@ VaeArgs vae_args(const p3d_vae* v, const float* x, const float* t, int64_t B, co
   a.w = v->params + v->P0; a.m = v->am + v->P0; a.v = v->av + v->P0; a.pk_out = v->pk; a.st = v->st;
   a.pkidx = v->pkidx;
   a.nblk = 1;
+  a.nterm = v->kind == P3D_VAE_KIND_BONES ? 4 : 3;
   return a;
 }
 
@@ -2842,8 +2856,9 @@ int vae_forward(p3d_vae* v, const float* x, const VaeCat* cat, int64_t B, const 
   if (cat) a.cat = *cat;
   const int64_t nwg = (B + 63) / 64;
   const int grid = (int)(nwg < v->cus ? nwg : v->cus);
-  if (cat) hipLaunchKernelGGL(k_vae_fwd_cat, dim3(grid), dim3(256), v->lds, st, a);
-  else hipLaunchKernelGGL(k_vae_fwd, dim3(grid), dim3(256), v->lds, st, a);
+  const bool bones = v->kind == P3D_VAE_KIND_BONES;
+  if (cat) hipLaunchKernelGGL(bones ? k_vae_bones_fwd_cat : k_vae_fwd_cat, dim3(grid), dim3(256), v->lds, st, a);
+  else hipLaunchKernelGGL(bones ? k_vae_bones_fwd : k_vae_fwd, dim3(grid), dim3(256), v->lds, st, a);
   LAUNCH_CHECK("k_vae_fwd");
   return P3D_OK;
 }
@@ -2855,7 +2870,8 @@ int vae_step(p3d_vae* v, const float* x, const VaeCat* cat, const float* t, int6
              const char* what) {
   if (!t || !factors || !loss3) return fail(P3D_ERR_ARG, std::string(what) + ": null argument");
   if (B > v->max_batch) return fail(P3D_ERR_ARG, std::string(what) + ": B exceeds max_batch");
-  if (factors[1] != 0.0f && v->desc.out != 48)
+  const bool bones = v->kind == P3D_VAE_KIND_BONES;
+  if (!bones && factors[1] != 0.0f && v->desc.out != 48)
     return fail(P3D_ERR_ARG, std::string(what) + ": the KCS term needs out == 48 (kcs_factor must be 0)");
   const hipStream_t st = (hipStream_t)stream;
   VaeWideArgs wa{};
@@ -2872,19 +2888,25 @@ int vae_step(p3d_vae* v, const float* x, const VaeCat* cat, const float* t, int6
   const bool one = nblk == 1 && v->form == 0;
   a.backward = backward; a.adam = adam; a.lr = lr;
   a.nblk = nblk;
-  a.c_like = (float)(2.0 * (double)factors[0] / ((double)B * v->desc.out));
-  a.c_kcs = (float)((double)factors[1] / (double)B);
+  if (bones) {   // factors = {mag, cos, dkl, ang} (losses.py:143-152)
+    a.c_like = (float)(2.0 * (double)factors[0] / (16.0 * (double)B));
+    a.c_cos = (float)((double)factors[1] / (8.0 * (double)B));
+    a.c_kcs = (float)((double)factors[3] / (256.0 * (double)B));
+  } else {
+    a.c_like = (float)(2.0 * (double)factors[0] / ((double)B * v->desc.out));
+    a.c_kcs = (float)((double)factors[1] / (double)B);
+  }
   a.c_kl = (float)((double)factors[2] / (double)B);
-  for (int j = 0; j < 3; ++j) a.f[j] = factors[j];
+  for (int j = 0; j < a.nterm; ++j) a.f[j] = factors[j];
   a.lpart = v->ws + (int64_t)nblk * v->desc.P;
   a.loss3 = loss3;
   a.gout = one ? v->grads + v->P0 : v->ws;
   a.tail = one;
   a.dx = v->wide ? v->ws + v->dz0_off : nullptr;
   const int grid = nblk < v->cus ? nblk : v->cus;
-  if (v->wide) hipLaunchKernelGGL(k_vae_step_dx, dim3(grid), dim3(256), v->lds, st, a);
-  else if (cat) hipLaunchKernelGGL(k_vae_step_cat, dim3(grid), dim3(256), v->lds, st, a);
-  else hipLaunchKernelGGL(k_vae_step, dim3(grid), dim3(256), v->lds, st, a);
+  if (v->wide) hipLaunchKernelGGL(bones ? k_vae_bones_step_dx : k_vae_step_dx, dim3(grid), dim3(256), v->lds, st, a);
+  else if (cat) hipLaunchKernelGGL(bones ? k_vae_bones_step_cat : k_vae_step_cat, dim3(grid), dim3(256), v->lds, st, a);
+  else hipLaunchKernelGGL(bones ? k_vae_bones_step : k_vae_step, dim3(grid), dim3(256), v->lds, st, a);
   LAUNCH_CHECK("k_vae_step");
   if (!one) {
     // the partials form: block sums (gradient and loss) and the optimizer, behind it on the stream
@@ -2927,16 +2949,30 @@ extern "C" int64_t p3d_vae_lds_bytes(int32_t in, int32_t n_enc, const int32_t* e
   std::vector<std::string> names;
   std::vector<VaeTensor> tensors;
   int P0;
-  return (int64_t)vae_full_layout(d, names, tensors, P0, in, n_enc, enc_dims, latent, n_dec, dec_dims, out);
+  return (int64_t)vae_full_layout(d, names, tensors, P0, P3D_VAE_KIND_ELBO, in, n_enc, enc_dims, latent, n_dec, dec_dims,
+                                  out);
 }
 
-extern "C" int p3d_vae_create(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent, int32_t n_dec,
-                              const int32_t* dec_dims, int32_t out, int32_t max_batch, uint64_t seed, p3d_vae** vout) {
+extern "C" int64_t p3d_vae_bones_lds_bytes(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent,
+                                           int32_t n_dec, const int32_t* dec_dims) {
+  if (vae_check_shape(in, n_enc, enc_dims, latent, n_dec, dec_dims, 64)) return 0;
+  VaeDesc d;
+  std::vector<std::string> names;
+  std::vector<VaeTensor> tensors;
+  int P0;
+  return (int64_t)vae_full_layout(d, names, tensors, P0, P3D_VAE_KIND_BONES, in, n_enc, enc_dims, latent, n_dec, dec_dims,
+                                  64);
+}
+
+namespace {
+int vae_create(int kind, int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent, int32_t n_dec,
+               const int32_t* dec_dims, int32_t out, int32_t max_batch, uint64_t seed, p3d_vae** vout) {
   if (!vout) return fail(P3D_ERR_ARG, "p3d_vae_create: null argument");
   if (int rc = vae_check_shape(in, n_enc, enc_dims, latent, n_dec, dec_dims, out)) return rc;
   if (max_batch < 1 || max_batch > (1 << 20)) return fail(P3D_ERR_ARG, "p3d_vae_create: max_batch must be in 1 .. 2^20");
   p3d_vae* v = new p3d_vae();
-  v->lds = vae_full_layout(v->desc, v->names, v->tensors, v->P0, in, n_enc, enc_dims, latent, n_dec, dec_dims, out);
+  v->kind = kind;
+  v->lds = vae_full_layout(v->desc, v->names, v->tensors, v->P0, kind, in, n_enc, enc_dims, latent, n_dec, dec_dims, out);
   v->wide = in > 256;
   v->in = in; v->n0 = enc_dims[0];
   v->Ptot = v->P0 + v->desc.P;
@@ -3006,7 +3042,12 @@ extern "C" int p3d_vae_create(int32_t in, int32_t n_enc, const int32_t* enc_dims
   for (const void* k : {(const void*)k_vae_fwd_cat, (const void*)k_vae_step_cat, (const void*)k_vae_step_dx})
     if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->lds)) != hipSuccess)
       return bail(e, "hipFuncSetAttribute(k_vae_*_cat)");
-  if (!v->wide && in % out == 0 && in / out <= P3D_VAE_SEQ_MAX_LEN) {
+  if (kind == P3D_VAE_KIND_BONES)
+    for (const void* k : {(const void*)k_vae_bones_fwd, (const void*)k_vae_bones_fwd_cat, (const void*)k_vae_bones_step,
+                          (const void*)k_vae_bones_step_cat, (const void*)k_vae_bones_step_dx})
+      if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->lds)) != hipSuccess)
+        return bail(e, "hipFuncSetAttribute(k_vae_bones_*)");
+  if (kind == P3D_VAE_KIND_ELBO && !v->wide && in % out == 0 && in / out <= P3D_VAE_SEQ_MAX_LEN) {
     const size_t sl = vae_seq_layout(v->desc, v->seq_xoff, v->seq_toff, v->seq_ldt, v->seq_moff);
     if (sl <= P3D_VAE_LDS_LIMIT) {
       v->seq_len = in / out;
@@ -3018,6 +3059,39 @@ extern "C" int p3d_vae_create(int32_t in, int32_t n_enc, const int32_t* enc_dims
     }
   }
   *vout = v;
+  return P3D_OK;
+}
+}  // namespace
+
+extern "C" int p3d_vae_create(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent, int32_t n_dec,
+                              const int32_t* dec_dims, int32_t out, int32_t max_batch, uint64_t seed, p3d_vae** vout) {
+  return vae_create(P3D_VAE_KIND_ELBO, in, n_enc, enc_dims, latent, n_dec, dec_dims, out, max_batch, seed, vout);
+}
+
+extern "C" int p3d_vae_create_bones(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent, int32_t n_dec,
+                                    const int32_t* dec_dims, int32_t max_batch, uint64_t seed, p3d_vae** vout) {
+  return vae_create(P3D_VAE_KIND_BONES, in, n_enc, enc_dims, latent, n_dec, dec_dims, 64, max_batch, seed, vout);
+}
+
+extern "C" int32_t p3d_vae_kind(const p3d_vae* v) { return v ? v->kind : -1; }
+
+extern "C" int p3d_bones_from_joints(const float* joints, int64_t B, int32_t precise, float* out64, void* stream) {
+  if (!joints || !out64) return fail(P3D_ERR_ARG, "p3d_bones_from_joints: null argument");
+  if (B < 1 || B > (1 << 20)) return fail(P3D_ERR_ARG, "p3d_bones_from_joints: B must be in 1 .. 2^20");
+  if (precise != 0 && precise != 1) return fail(P3D_ERR_ARG, "p3d_bones_from_joints: precise must be 0 or 1");
+  const unsigned grid = (unsigned)((B * 16 + 255) / 256);
+  if (precise) hipLaunchKernelGGL(k_bones_from_joints<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, joints, B, out64);
+  else hipLaunchKernelGGL(k_bones_from_joints<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, joints, B, out64);
+  LAUNCH_CHECK("k_bones_from_joints");
+  return P3D_OK;
+}
+
+extern "C" int p3d_bones_to_joints(const float* bones64, int64_t B, double* joints_f64, void* stream) {
+  if (!bones64 || !joints_f64) return fail(P3D_ERR_ARG, "p3d_bones_to_joints: null argument");
+  if (B < 1 || B > (1 << 20)) return fail(P3D_ERR_ARG, "p3d_bones_to_joints: B must be in 1 .. 2^20");
+  hipLaunchKernelGGL(k_bones_to_joints, dim3((unsigned)((B * 16 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, bones64,
+                     B, joints_f64);
+  LAUNCH_CHECK("k_bones_to_joints");
   return P3D_OK;
 }
 
@@ -3209,7 +3283,8 @@ extern "C" int64_t p3d_vae_seq_lds_bytes(int32_t in, int32_t n_enc, const int32_
   if (in > 256 || in % out != 0 || in / out > P3D_VAE_SEQ_MAX_LEN) return 0;
   VaeDesc d;
   std::vector<std::string> names;
-  if (vae_best_layout(d, names, in, n_enc, enc_dims, latent, n_dec, dec_dims, out) > P3D_VAE_LDS_LIMIT) return 0;
+  if (vae_best_layout(d, names, P3D_VAE_KIND_ELBO, in, n_enc, enc_dims, latent, n_dec, dec_dims, out) > P3D_VAE_LDS_LIMIT)
+    return 0;
   int xoff, toff, ldt, moff;
   return (int64_t)vae_seq_layout(d, xoff, toff, ldt, moff);   // (both forms run one tile per workgroup)
 }
@@ -3225,6 +3300,7 @@ extern "C" int p3d_vae_seq_filter(p3d_vae* v, const float* pred, const int64_t* 
                                   float* state, int32_t* started, float* ref, float* frame_err, double* seq_err,
                                   void* stream) {
   if (!v || !pred || !seq_off || !ref) return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: null argument");
+  if (v->kind != P3D_VAE_KIND_ELBO) return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: a bones filter has no sequence form");
   if (v->wide || v->desc.in % v->desc.out != 0 || v->desc.in / v->desc.out > P3D_VAE_SEQ_MAX_LEN)
     return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: in must be seq_len * out with seq_len in 1 .. " +
                                  std::to_string(P3D_VAE_SEQ_MAX_LEN));

@@ -31,14 +31,22 @@
 // VaeCat (column segments, each optionally row-indexed; p3d.h p3d_vae_cat) instead of x, in the
 // same order of operations; k_vae_step_dx is the core of the wide form (p3d_vae_wide.h), whose
 // input is layer 0's output and whose backward also leaves the data gradient at that input.
+//
+// The bones filter (models.py:544-573 VAEBones, losses.py:113-156 loss_bones) is the same body
+// with another loss kind: its decoder ends dec_dim -> mag1 (16, ReLU) -> {mag2 (16), cos2 (48)},
+// the two linear heads one packed layer [16, 64] split at column 16 like the mean / log_varianze
+// head, and k_vae_bones_fwd / _step and their _cat and _dx forms form the four-term loss and its
+// backward in place of the ELBO's.
 #pragma once
 #include "p3d_kernels.h"
 #include "p3d_layers.h"   // p3d_adam1
 #include <math.h>
 #include <stdint.h>
 
-#define P3D_VAE_MAX_L 10          // 4 encoder layers + the head + 4 decoder layers + the output
-#define P3D_VAE_MAX_T 22          // kernel + bias of every dense layer (the head is two layers)
+#define P3D_VAE_MAX_L 11          // 4 encoder layers + the head + 4 decoder layers (+ mag1) + the output
+#define P3D_VAE_MAX_T 26          // kernel + bias of every dense layer (the head and the bones output are two layers)
+#define P3D_VAE_KIND_ELBO 0       // y [out] against the joints: likelihood, KCS, KL
+#define P3D_VAE_KIND_BONES 1      // y [64] = [mag | cos] against the bones: MAG, COS, KL, ANG (models.py:544-573)
 #define P3D_VAE_SITE 0x564145     // Philox site id of the eps stream (dropout sites are < 64)
 #define P3D_VAE_LDS_LIMIT 163840  // one workgroup's LDS on gfx950
 
@@ -156,12 +164,14 @@ struct VaeArgs {
   // step
   int backward, adam, nblk;
   int tail;                   // one-launch form: k_vae_step forms the loss and applies Adam itself (nblk == 1)
-  float c_like, c_kcs, c_kl;  // 2 likef / (B out), kcsf / B, dklf / B
-  float f[3];                 // likef, kcsf, dklf
+  float c_like, c_kcs, c_kl;  // 2 likef / (B out), kcsf / B, dklf / B; bones: 2 magf / (16 B), angf / (256 B), dklf / B
+  float c_cos;                // bones: cosf / (8 B)
+  int nterm;                  // row terms and loss entries: 3, bones 4
+  float f[4];                 // likef, kcsf, dklf; bones: magf, cosf, dklf, angf
   float lr;
   float* gout;                // block b's partial gradient at gout + b * P
   float* lpart;               // block b's loss sums at lpart + 4 b
-  float* loss3;               // one-launch forms: the loss 3-vector
+  float* loss3;               // the loss vector [nterm]
   float* w; float* m; float* v; float* pk_out; VaeState* st;
   const int* pkidx;           // flat element -> its place in the packed copy
   float* dx;                  // k_vae_step_dx: d(loss sum) / dx, [B, in]
@@ -217,13 +227,103 @@ __device__ __forceinline__ void vae_layer_fwd_cat(const VaeLayer& L, const VaeCa
   }
 }
 
+// The bones loss of one tile (losses.py:113-156) on y = [mag (16) | cos (16 x 3)] in `yb` against the
+// target row [tm | tc]: row terms MAG = mean_16 (tm - pm)^2, COS = 3 mean_48 (tc - pc)^2 and ANG =
+// mean_16x16 |G(tc) - G(pc)|, G(c)[a][b] = c[a] . c[b] -- the KCS block on the 16 cosine triples
+// themselves (no parent subtraction).  With `train`, dy = d(loss sum) / dy in place of y:
+//   d / dpm = c_like (pm - tm), d / dpc = c_cos (pc - tc) + c_kcs 2 sum_b sign(phi[a][b]) pc[b],
+// phi = G(pc) - G(tc), sign(0) = 0, sign(NaN) = NaN.
+__device__ __forceinline__ void vae_bones_terms(const VaeArgs& a, const VaeDesc* d, float* act, float* yb, int ldy,
+                                                int64_t row0, bool train, float terms[4]) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63, i = lane & 15, q = lane >> 4;
+  const int64_t Bm1 = a.B - 1;
+  const int64_t myrow = row0 + i < a.B ? row0 + i : Bm1;
+  const bool myvalid = row0 + i < a.B;
+  const float* trow = a.t + myrow * 64;
+  {
+    float p = 0.0f;
+    for (int c = q; c < 16; c += 4) {
+      const float df = trow[c] - yb[i * ldy + c];
+      p += df * df;
+    }
+    terms[0] = vae_rowsum4(p) / 16.0f;
+    p = 0.0f;
+    for (int c = q; c < 48; c += 4) {
+      const float df = trow[16 + c] - yb[i * ldy + 16 + c];
+      p += df * df;
+    }
+    terms[1] = 3.0f * (vae_rowsum4(p) / 48.0f);
+  }
+  float* bt = act + d->bt;
+  const int ldb = d->ldb;
+  for (int idx = lane; idx < 16 * 48; idx += 64) {
+    const int r = idx / 48, e = idx - r * 48;
+    const int64_t grow = row0 + r < a.B ? row0 + r : Bm1;
+    bt[r * ldb + e] = a.t[grow * 64 + 16 + e];
+  }
+  vae_wsync();
+  const float* yc = yb + i * ldy + 16;
+  float pa[4][3], ta[4][3], dB[4][3];
+#pragma unroll
+  for (int a4 = 0; a4 < 4; ++a4) {
+    const int bn = 4 * q + a4;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      pa[a4][c] = yc[3 * bn + c];
+      ta[a4][c] = bt[i * ldb + 3 * bn + c];
+      dB[a4][c] = 0.0f;
+    }
+  }
+  float s = 0.0f;
+  for (int b = 0; b < 16; ++b) {
+    float pb[3], tb[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      pb[c] = yc[3 * b + c];
+      tb[c] = bt[i * ldb + 3 * b + c];
+    }
+#pragma unroll
+    for (int a4 = 0; a4 < 4; ++a4) {
+      const float pp = (pa[a4][0] * pb[0] + pa[a4][1] * pb[1]) + pa[a4][2] * pb[2];
+      const float tt = (ta[a4][0] * tb[0] + ta[a4][1] * tb[1]) + ta[a4][2] * tb[2];
+      const float phi = pp - tt;
+      s += fabsf(phi);
+      const float sg = phi > 0.0f ? 1.0f : (phi < 0.0f ? -1.0f : (phi == 0.0f ? 0.0f : phi));   // as the KCS block
+#pragma unroll
+      for (int c = 0; c < 3; ++c) dB[a4][c] += sg * pb[c];
+    }
+  }
+  terms[3] = vae_rowsum4(s) * 0.00390625f;   // / 256
+  vae_wsync();   // every lane has read the target cosines
+  if (!train) return;
+  const float ck = myvalid ? 2.0f * a.c_kcs : 0.0f;
+#pragma unroll
+  for (int a4 = 0; a4 < 4; ++a4)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) bt[i * ldb + 3 * (4 * q + a4) + c] = ck * dB[a4][c];
+  vae_wsync();
+  for (int idx = lane; idx < 16 * 64; idx += 64) {
+    const int r = idx >> 6, e = idx & 63;
+    const bool valid = row0 + r < a.B;
+    const int64_t grow = valid ? row0 + r : Bm1;
+    float g = 0.0f;
+    float cl = a.c_like;
+    if (e >= 16) { g = bt[r * ldb + (e - 16)]; cl = a.c_cos; }
+    cl = valid ? cl : 0.0f;
+    g += cl * (yb[r * ldy + e] - a.t[grow * 64 + e]);
+    yb[r * ldy + e] = g;
+  }
+}
+
 // Forward of one tile (rows row0 .. row0 + 15) through every layer, the reparametrisation, the
 // requested global outputs and the three per-row loss terms (when a.t is set); with `train` also
 // 0.5 eps std, and dy = d(loss sum) / dy in place of y.  Returns this lane's row terms (lanes of
-// one row hold the same values).
-template <bool CAT>
+// one row hold the same values).  KIND picks the loss at compile time: the ELBO's three terms, or
+// the bones filter's four (vae_bones_terms; terms[2], the KL term, is common).
+template <bool CAT, int KIND>
 __device__ __forceinline__ void vae_tile_fwd(const VaeArgs& a, const VaeDesc* d, const float* W, float* act,
-                                             int64_t row0, uint64_t ctr, bool train, float terms[3]) {
+                                             int64_t row0, uint64_t ctr, bool train, float terms[4]) {
   const int lane = threadIdx.x & 63, i = lane & 15, q = lane >> 4;
   const int lat = d->latent, out = d->out;
   const int64_t Bm1 = a.B - 1;
@@ -287,7 +387,7 @@ __device__ __forceinline__ void vae_tile_fwd(const VaeArgs& a, const VaeDesc* d,
       }
     }
   }
-  terms[0] = terms[1] = terms[2] = 0.0f;
+  terms[0] = terms[1] = terms[2] = terms[3] = 0.0f;
   if (a.t) {   // KL row term 0.5 sum(exp(lv) + mean^2 - 1 - lv) (losses.py:29)
 #pragma clang fp contract(off)
     float p = 0.0f;
@@ -313,6 +413,10 @@ __device__ __forceinline__ void vae_tile_fwd(const VaeArgs& a, const VaeDesc* d,
     }
   }
   if (!a.t) return;
+  if (KIND == P3D_VAE_KIND_BONES) {
+    vae_bones_terms(a, d, act, yb, ldy, row0, train, terms);
+    return;
+  }
   const float* trow = a.t + myrow * out;
   {   // likelihood row term mean_D (t - y)^2 (losses.py:31)
 #pragma clang fp contract(off)
@@ -413,7 +517,7 @@ __device__ __forceinline__ void vae_load_params(const VaeArgs& a, const VaeDesc*
 
 // The filter: x -> mean, log_var -> z -> y, every output optional.  Waves stride over the 16-row
 // tiles on their own: no barrier after the parameter load.
-template <bool CAT>
+template <bool CAT, int KIND>
 __device__ __forceinline__ void vae_fwd_body(const VaeArgs& a) {
   extern __shared__ f32x4 vae_smem[];
   float* sm = (float*)vae_smem;
@@ -424,19 +528,21 @@ __device__ __forceinline__ void vae_fwd_body(const VaeArgs& a) {
   const uint64_t ctr = a.ctr_dev ? (uint64_t)a.ctr_dev->step : a.ctr;
   const int64_t ntiles = (a.B + 15) >> 4;
   for (int64_t tile = (int64_t)blockIdx.x * 4 + wave; tile < ntiles; tile += (int64_t)gridDim.x * 4) {
-    float terms[3];
-    vae_tile_fwd<CAT>(a, d, sm, act, tile * 16, ctr, false, terms);
+    constexpr int NTERM = KIND == P3D_VAE_KIND_BONES ? 4 : 3;
+    float terms[4];
+    vae_tile_fwd<CAT, KIND>(a, d, sm, act, tile * 16, ctr, false, terms);
     const int64_t row = tile * 16 + (lane & 15);
     if (a.row_terms && a.t && lane < 16 && row < a.B) {
-      a.row_terms[row * 3 + 0] = terms[0];
-      a.row_terms[row * 3 + 1] = terms[1];
-      a.row_terms[row * 3 + 2] = terms[2];
+#pragma unroll
+      for (int j = 0; j < NTERM; ++j) a.row_terms[row * NTERM + j] = terms[j];
     }
     vae_wsync();
   }
 }
-__global__ __launch_bounds__(256) void k_vae_fwd(VaeArgs a) { vae_fwd_body<false>(a); }
-__global__ __launch_bounds__(256) void k_vae_fwd_cat(VaeArgs a) { vae_fwd_body<true>(a); }
+__global__ __launch_bounds__(256) void k_vae_fwd(VaeArgs a) { vae_fwd_body<false, P3D_VAE_KIND_ELBO>(a); }
+__global__ __launch_bounds__(256) void k_vae_fwd_cat(VaeArgs a) { vae_fwd_body<true, P3D_VAE_KIND_ELBO>(a); }
+__global__ __launch_bounds__(256) void k_vae_bones_fwd(VaeArgs a) { vae_fwd_body<false, P3D_VAE_KIND_BONES>(a); }
+__global__ __launch_bounds__(256) void k_vae_bones_fwd_cat(VaeArgs a) { vae_fwd_body<true, P3D_VAE_KIND_BONES>(a); }
 
 __device__ __forceinline__ float vae_alpha(const VaeState* st, float lr) {
 #pragma clang fp contract(off)
@@ -488,7 +594,7 @@ __device__ __forceinline__ void vae_adam_tail(const VaeArgs& a, int P, float alp
   }
 }
 
-// loss3 = factor * (sum over blocks, in block order, of the blocks' row-term sums) / B
+// loss[j] = factor * (sum over blocks, in block order, of the blocks' row-term sums) / B
 __device__ __forceinline__ void vae_loss3(const VaeArgs& a, int j) {
 #pragma clang fp contract(off)
   float s = a.lpart[j];
@@ -501,8 +607,9 @@ __device__ __forceinline__ void vae_loss3(const VaeArgs& a, int j) {
 // CAT: the input through a.cat.  DX (the wide form's core, whose input is layer 0's ReLU output):
 // the data gradient runs for layer 0 too and goes to a.dx; alpha is always left
 // in the state for the layer-0 optimizer behind this launch.
-template <bool CAT, bool DX>
+template <bool CAT, bool DX, int KIND>
 __device__ __forceinline__ void vae_step_body(const VaeArgs& a) {
+  constexpr int NTERM = KIND == P3D_VAE_KIND_BONES ? 4 : 3;
   extern __shared__ f32x4 vae_smem[];
   float* sm = (float*)vae_smem;
   const VaeDesc* d = a.desc;
@@ -520,15 +627,15 @@ __device__ __forceinline__ void vae_step_body(const VaeArgs& a) {
   const int nl = d->nl;
   for (int blk = blockIdx.x; blk < a.nblk; blk += gridDim.x) {
     const int64_t row0 = (int64_t)blk * 64 + wave * 16;
-    float terms[3];
-    vae_tile_fwd<CAT>(a, d, sm, act, row0, ctr, a.backward != 0, terms);
+    float terms[4];
+    vae_tile_fwd<CAT, KIND>(a, d, sm, act, row0, ctr, a.backward != 0, terms);
     if (lane < 16) {
       const bool valid = row0 + i < a.B;
 #pragma unroll
-      for (int j = 0; j < 3; ++j) rt[(wave * 16 + i) * 4 + j] = valid ? terms[j] : 0.0f;
+      for (int j = 0; j < NTERM; ++j) rt[(wave * 16 + i) * 4 + j] = valid ? terms[j] : 0.0f;
     }
     __syncthreads();
-    if (tid < 3) {   // the block's row-term sums, rows in order
+    if (tid < NTERM) {   // the block's row-term sums, rows in order
       float s = rt[tid];
       for (int r = 1; r < 64; ++r) s += rt[4 * r + tid];
       a.lpart[4 * blk + tid] = s;
@@ -661,16 +768,19 @@ __device__ __forceinline__ void vae_step_body(const VaeArgs& a) {
     if (a.backward && a.adam) {
       vae_adam_tail(a, d->P, alpha);
     }
-    if (tid < 3) vae_loss3(a, tid);
+    if (tid < NTERM) vae_loss3(a, tid);
     if (a.backward && a.adam) {
       __syncthreads();   // every thread has formed alpha from the old state
       if (tid == 0) vae_advance(a.st);
     }
   }
 }
-__global__ __launch_bounds__(256) void k_vae_step(VaeArgs a) { vae_step_body<false, false>(a); }
-__global__ __launch_bounds__(256) void k_vae_step_cat(VaeArgs a) { vae_step_body<true, false>(a); }
-__global__ __launch_bounds__(256) void k_vae_step_dx(VaeArgs a) { vae_step_body<false, true>(a); }
+__global__ __launch_bounds__(256) void k_vae_step(VaeArgs a) { vae_step_body<false, false, P3D_VAE_KIND_ELBO>(a); }
+__global__ __launch_bounds__(256) void k_vae_step_cat(VaeArgs a) { vae_step_body<true, false, P3D_VAE_KIND_ELBO>(a); }
+__global__ __launch_bounds__(256) void k_vae_step_dx(VaeArgs a) { vae_step_body<false, true, P3D_VAE_KIND_ELBO>(a); }
+__global__ __launch_bounds__(256) void k_vae_bones_step(VaeArgs a) { vae_step_body<false, false, P3D_VAE_KIND_BONES>(a); }
+__global__ __launch_bounds__(256) void k_vae_bones_step_cat(VaeArgs a) { vae_step_body<true, false, P3D_VAE_KIND_BONES>(a); }
+__global__ __launch_bounds__(256) void k_vae_bones_step_dx(VaeArgs a) { vae_step_body<false, true, P3D_VAE_KIND_BONES>(a); }
 
 // B > 64: block partials summed in block order into the gradient buffer, then Adam.  Also the
 // stand-alone optimizer over the gradient buffer (nblk == 1, partials == the buffer itself).
@@ -684,7 +794,7 @@ __global__ __launch_bounds__(256) void k_vae_reduce_adam(VaeArgs a, float* __res
     if (a.adam) vae_adam_elem(a, d, e, g, a.st->alpha);
   }
   if (blockIdx.x == 0) {
-    if (a.loss3 && threadIdx.x < 3) vae_loss3(a, threadIdx.x);
+    if (a.loss3 && threadIdx.x < a.nterm) vae_loss3(a, threadIdx.x);
     if (a.adam && threadIdx.x == 0) vae_advance(a.st);   // (nothing in this launch reads the beta powers)
   }
 }

@@ -27,6 +27,12 @@ def build_parser():
     p.add_argument("--likelihood_factor", type=float, default=1.0, help="Term to regularize the likelihood loss for ELBO")
     p.add_argument("--dkl_factor", type=float, default=1.0, help="Term to regularize the likelihood loss for ELBO")
     p.add_argument("--kcs_factor", type=float, default=1.0, help="Term to regularize the likelihood loss for ELBO")
+    # the bones loss's factors: the reference reads them from src/train.yml alone (losses.py:143-152)
+    p.add_argument("--mag_factor", type=float, default=1.0, help="Term to regularize the bone-length loss")
+    p.add_argument("--cos_factor", type=float, default=1.0, help="Term to regularize the direction-cosine loss")
+    p.add_argument("--ang_factor", type=float, default=1.0, help="Term to regularize the angle (Gram matrix) loss")
+    p.add_argument("--bones_mapping_dir", type=str, default="src/bones_mapping.yml",
+                   help="File with the bones mapping (the built-in skeleton when the driver is not given one)")
     p.add_argument("--max_norm", action='store_true', default=False, help="Apply maxnorm constraint to the weights")
     p.add_argument("--residual", action='store_true', default=False,
                    help="Whether to add a residual connection every 2 layers")

@@ -20,6 +20,22 @@ def _factors():
     return (f.likelihood_factor, f.kcs_factor, f.dkl_factor)
 
 
+def _bones_factors():
+    f = ENV.FLAGS
+    return (f.mag_factor, f.cos_factor, f.dkl_factor, f.ang_factor)
+
+
+def loss_bones(model, inputs, targets, eps=None):
+    """The bones loss (losses.py:113-156): the device 4-vector [MAG, COS, DKL, ANG] under FLAGS'
+    factors -- one launch; the tensor is the model's loss buffer.  `model` is a VAEBones, `targets`
+    the [B, 64] bones tensor [mag | cos] or the reference's (magnitudes, dir_cos) pair."""
+    if isinstance(targets, (tuple, list)):
+        import torch
+        targets = torch.cat([torch.as_tensor(targets[0]), torch.as_tensor(targets[1])], dim=1)
+    model._calls += 1
+    return model.loss_device(inputs, targets, _bones_factors(), eps=eps, ctr=model._calls)
+
+
 class ELBO():
     @classmethod
     def compute_loss(cls, model, inputs, targets, eps=None):

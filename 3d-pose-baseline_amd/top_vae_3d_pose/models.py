@@ -1,5 +1,5 @@
 """The VAE pose filter and the lifter + filter model (src/top_vae_3d_pose/models.py:12-91 VAE,
-:485-540 Pose3DVae) over libp3d.so's p3d_vae_* entry points (csrc/p3d_vae.h).
+:485-540 Pose3DVae, :544-573 VAEBones) over libp3d.so's p3d_vae_* entry points (csrc/p3d_vae.h).
 
 The reference's names are kept so that its scripts drop in.  Everything runs on the GPU; there is
 no CPU fallback.  tf.random.normal's stream cannot be reproduced: eps comes from the library's
@@ -14,6 +14,7 @@ import numpy as np
 
 import _p3d
 from _p3d import check, lib, ptr
+from top_vae_3d_pose import bones
 
 HUMAN_3D_SIZE = 48
 HUMAN_2D_SIZE = 32
@@ -21,6 +22,9 @@ HUMAN_2D_SIZE = 32
 
 class VAE(object):
     """Variational autoencoder input_size -> enc_dim -> {mean, log_varianze} -> dec_dim -> human_3d_size."""
+
+    N_TERMS = 3          # entries of the loss vector and of a row of row_terms
+    BONES = False        # VAEBones: the library's bones kind (p3d_vae_create_bones)
 
     def __init__(self, input_size, latent_dim, enc_dim, dec_dim, human_3d_size=HUMAN_3D_SIZE, *, max_batch=4096,
                  seed=None, device=None, init=True):
@@ -38,16 +42,19 @@ class VAE(object):
         enc = (ctypes.c_int32 * max(len(self.enc_dim), 1))(*self.enc_dim)
         dec = (ctypes.c_int32 * max(len(self.dec_dim), 1))(*self.dec_dim)
         h = ctypes.c_void_p()
-        args = (self.input_size, len(self.enc_dim), enc, self.latent_dim, len(self.dec_dim), dec,
-                self.human_3d_size, self.max_batch, self.seed, ctypes.byref(h))
+        self.output_size = 64 if self.BONES else self.human_3d_size     # width of y and of a target row
+        args = (self.input_size, len(self.enc_dim), enc, self.latent_dim, len(self.dec_dim), dec)
+        args += (() if self.BONES else (self.human_3d_size,)) + (self.max_batch, self.seed, ctypes.byref(h))
+        create, what = ((lib().p3d_vae_create_bones, "p3d_vae_create_bones") if self.BONES else
+                        (lib().p3d_vae_create, "p3d_vae_create"))
         if torch.cuda.is_available():
             self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
             with torch.cuda.device(self.device):
-                check(lib().p3d_vae_create(*args), "p3d_vae_create")
+                check(create(*args), what)
         else:   # argument errors answer without a GPU; a valid shape then fails on the missing device
-            rc = lib().p3d_vae_create(*args)
+            rc = create(*args)
             if rc == _p3d.P3D_ERR_ARG:
-                check(rc, "p3d_vae_create")
+                check(rc, what)
             raise _p3d.P3DError("VAE needs a ROCm GPU (torch.cuda.is_available() is False); "
                                 "the HIP path has no CPU fallback")
         self._h = h
@@ -63,7 +70,7 @@ class VAE(object):
             shape = (cols.value,) if nm.endswith("/bias") else (rows.value, cols.value)
             self.param_table.append((nm, shape, off.value))
         self._flat = {}
-        self._loss = torch.zeros(3, dtype=torch.float32, device=self.device)
+        self._loss = torch.zeros(self.N_TERMS, dtype=torch.float32, device=self.device)
         self._calls = 0     # eps counter of inference calls
         if init:
             self.initialize(self.seed)
@@ -200,7 +207,9 @@ class VAE(object):
         return cat, B, keep
 
     def _factors(self, factors):
-        return (ctypes.c_float * 3)(*[float(f) for f in factors])
+        if len(factors) != self.N_TERMS:
+            raise ValueError("factors: expected %d values, got %d" % (self.N_TERMS, len(factors)))
+        return (ctypes.c_float * self.N_TERMS)(*[float(f) for f in factors])
 
     # ------------------------------------------------------------------ device entry points
     def forward_device(self, x, eps=None, ctr=0, target=None, want=("y",)):
@@ -216,13 +225,13 @@ class VAE(object):
         eps = None if eps is None else self._dev(eps, self.latent_dim, "eps")
         if eps is not None and eps.shape[0] != B:
             raise ValueError("eps: expected %d rows, got %d" % (B, eps.shape[0]))
-        target = None if target is None else self._dev(target, self.human_3d_size, "target")
+        target = None if target is None else self._dev(target, self.output_size, "target")
         if target is not None and target.shape[0] != B:
             raise ValueError("target: expected %d rows, got %d" % (B, target.shape[0]))
-        widths = {"y": self.human_3d_size, "mean": self.latent_dim, "log_var": self.latent_dim, "z": self.latent_dim}
+        widths = {"y": self.output_size, "mean": self.latent_dim, "log_var": self.latent_dim, "z": self.latent_dim}
         out = {k: torch.empty((B, widths[k]), dtype=torch.float32, device=self.device) for k in want if k in widths}
         if target is not None:
-            out["row_terms"] = torch.empty((B, 3), dtype=torch.float32, device=self.device)
+            out["row_terms"] = torch.empty((B, self.N_TERMS), dtype=torch.float32, device=self.device)
         fn, what, xin = ((lib().p3d_vae_forward, "p3d_vae_forward", ptr(x)) if cat is None else
                          (lib().p3d_vae_forward_cat, "p3d_vae_forward_cat", ctypes.byref(cat)))
         check(fn(self._h, xin, B, ptr(eps), int(ctr), ptr(out.get("y")), ptr(out.get("mean")),
@@ -239,13 +248,15 @@ class VAE(object):
         else:
             x = self._dev(x, self.input_size, "vae input")
             B, xin = x.shape[0], ptr(x)
-        t = self._dev(t, self.human_3d_size, "target")
+        t = self._dev(t, self.output_size, "target")
         if t.shape[0] != B:
             raise ValueError("target: expected %d rows, got %d" % (B, t.shape[0]))
         eps = None if eps is None else self._dev(eps, self.latent_dim, "eps")
         if eps is not None and eps.shape[0] != B:
             raise ValueError("eps: expected %d rows, got %d" % (B, eps.shape[0]))
         loss = self._loss if loss_out is None else loss_out
+        if loss_out is not None and int(loss_out.numel()) < self.N_TERMS:
+            raise ValueError("loss_out: expected room for %d floats" % self.N_TERMS)
         check(fn(self._h, xin, ptr(t), B, ptr(eps), *middle, ptr(loss), self.stream()), what)
         return loss
 
@@ -273,6 +284,8 @@ class VAE(object):
 
     # ------------------------------------------------------------------ the recurrence over sequences
     def _seq_len(self):
+        if self.BONES:
+            raise ValueError("filter_sequences: a bones filter has no sequence form")
         if self.input_size > 256:
             raise ValueError("filter_sequences: a wide filter (input_size %d > 256) has no sequence form"
                              % self.input_size)
@@ -404,6 +417,27 @@ class VAE(object):
             pass
 
 
+class VAEBones(VAE):
+    """Variational autoencoder for bones (models.py:544-573): the decoder ends dec_dim -> mag1 (16,
+    ReLU) -> {mag2 (16), cos2 (48)}.  The device output is one [B, 64] tensor [mag | cos]
+    (forward_device's 'y', a target row, bones.convert_to_bones's result); calling the model returns
+    the (mag, cos) views of it.  Loss vectors are [MAG, COS, DKL, ANG] under factors (mag, cos, dkl,
+    ang) (losses.py:113-156).  The reference's layer 'cos1' feeds nothing and is not built."""
+
+    N_TERMS = 4
+    BONES = True
+
+    def __init__(self, input_size, latent_dim, enc_dim, dec_dim, human_3d_size=HUMAN_3D_SIZE, **kw):
+        if int(human_3d_size) != HUMAN_3D_SIZE:
+            raise ValueError("VAEBones: human_3d_size must be %d (16 bones), got %s" % (HUMAN_3D_SIZE, human_3d_size))
+        super(VAEBones, self).__init__(input_size, latent_dim, enc_dim, dec_dim, human_3d_size, **kw)
+
+    def __call__(self, inputs, training=False, eps=None):
+        self._calls += 1
+        y = self.forward_device(inputs, eps=eps, ctr=self._calls)["y"]
+        return y[:, :16], y[:, 16:]
+
+
 class Pose3DVae(object):
     """The frozen lifter + the VAE filter (models.py:485-540): call(x2d) -> (out_3d, out_vae), both
     on the device with no host round trip between p3d_serve and p3d_vae_forward."""
@@ -416,7 +450,7 @@ class Pose3DVae(object):
             raise NotImplementedError("Pose3DVae(use_effnet_ouptut=True) is served by Pose3DVaeCat (precomputed "
                                       "EfficientNet features as a segment of the filter's input)")
         if pred_bones:
-            raise NotImplementedError("Pose3DVae(pred_bones=True) (VAEBones) is not built")
+            raise NotImplementedError("Pose3DVae(pred_bones=True) is served by Pose3DVaeBones (VAEBones)")
         if pose3d is None:
             raise ValueError("Pose3DVae needs the lifter: pass pose3d=LinearModel(...) (the reference builds its "
                              "PoseBase here; this package's lifter is linear_model.LinearModel)")
@@ -454,7 +488,7 @@ class Pose3DVaeCat(object):
     def __init__(self, latent_dim, enc_dim, dec_dim, use_effnet_ouptut=False, use_2d=False, pred_bones=False, *,
                  pose3d=None, effnet_size=1280, max_batch=4096, seed=None):
         if pred_bones:
-            raise NotImplementedError("Pose3DVaeCat(pred_bones=True) (VAEBones) is not built")
+            raise NotImplementedError("Pose3DVaeCat(pred_bones=True) is served by Pose3DVaeBones (VAEBones)")
         if pose3d is None:
             raise ValueError("Pose3DVaeCat needs the lifter: pass pose3d=LinearModel(...)")
         if pose3d.output_size != HUMAN_3D_SIZE:
@@ -475,7 +509,8 @@ class Pose3DVaeCat(object):
         segs = [inputs, out_3d] if self.use_2d else [out_3d]
         if self.use_effnet_ouptut:
             if effnet_output is None:
-                raise ValueError("Pose3DVaeCat: this model was built with use_effnet_ouptut: pass effnet_output")
+                raise ValueError("%s: this model was built with use_effnet_ouptut: pass effnet_output"
+                                 % type(self).__name__)
             table, idx = effnet_output if isinstance(effnet_output, (tuple, list)) else (effnet_output, None)
             if not isinstance(table, torch.Tensor):
                 table = torch.from_numpy(np.array(table, dtype=np.float32, order="C")).to(self.vae.device)
@@ -486,7 +521,7 @@ class Pose3DVaeCat(object):
                 raise ValueError("effnet_output: expected %d rows, got %d" % (B, n))
             segs.append(table if idx is None else (table, idx))
         elif effnet_output is not None:
-            raise ValueError("Pose3DVaeCat: effnet_output given to a model built without use_effnet_ouptut")
+            raise ValueError("%s: effnet_output given to a model built without use_effnet_ouptut" % type(self).__name__)
         return segs
 
     def __call__(self, inputs, effnet_output=None, training=False, eps=None):
@@ -498,6 +533,57 @@ class Pose3DVaeCat(object):
         self.vae._calls += 1
         y = self.vae.forward_device(self.segments(inputs, out_3d, effnet_output), eps=eps, ctr=self.vae._calls)["y"]
         return out_3d, y
+
+    def save_weights(self, path):
+        self.vae.save_weights(path)
+
+    def load_weights(self, path):
+        self.vae.load_weights(path)
+
+    def close(self):
+        self.vae.close()
+
+
+class Pose3DVaeBones(object):
+    """The frozen lifter + the bones filter (models.py:485-540 built with pred_bones):
+    call(x2d, effnet_output) -> (out_3d, (mag, cos)).  The filter's input is
+    [inputs?] | bones(out_3d) | [effnet_output?] (models.py:528-536), the bones 16 lengths and 48
+    direction cosines (models.py:495-502); the concatenation is formed inside the filter's kernels.
+    The call converts with the float64 arithmetic of bones.convert_to_bones (models.py:529);
+    bones_tf() is the float32 form of the training step (pose_3d_bones.py:162-165)."""
+
+    def __init__(self, latent_dim, enc_dim, dec_dim, use_effnet_ouptut=False, use_2d=False, *, pose3d=None,
+                 effnet_size=1280, max_batch=4096, seed=None):
+        if pose3d is None:
+            raise ValueError("Pose3DVaeBones needs the lifter: pass pose3d=LinearModel(...)")
+        if pose3d.output_size != HUMAN_3D_SIZE:
+            raise ValueError("Pose3DVaeBones: the lifter must predict %d outputs, not %d"
+                             % (HUMAN_3D_SIZE, pose3d.output_size))
+        self.use_2d, self.use_effnet_ouptut, self.pred_bones = bool(use_2d), bool(use_effnet_ouptut), True
+        self.human_3d_size, self.human_2d_size = HUMAN_3D_SIZE, HUMAN_2D_SIZE
+        self.effnet_size = int(effnet_size)
+        self.pose3d = pose3d
+        self.bones_joints = bones.get_bones_joints()
+        self.input_size = (HUMAN_2D_SIZE if use_2d else 0) + 64 + (self.effnet_size if use_effnet_ouptut else 0)
+        self.vae = VAEBones(self.input_size, latent_dim, enc_dim, dec_dim, max_batch=max_batch, seed=seed,
+                            device=pose3d.device.index)
+
+    segments = Pose3DVaeCat.segments      # (the middle segment is the bones tensor)
+
+    def bones_tf(self, out_3d, out=None):
+        """The lifter's output as bones in float32 arithmetic (convert_to_bones_tf), one launch."""
+        return bones.convert_to_bones(out_3d, precise=False, out=out)
+
+    def __call__(self, inputs, effnet_output=None, training=False, eps=None):
+        torch = self.vae.torch
+        if not isinstance(inputs, torch.Tensor):
+            inputs = torch.from_numpy(np.array(inputs, dtype=np.float32, order="C"))
+        inputs = inputs.to(device=self.vae.device, dtype=torch.float32).contiguous()
+        out_3d = self.pose3d.serve_device(inputs)      # raises ValueError on a bad shape
+        b64 = bones.convert_to_bones(out_3d, self.bones_joints, precise=True)
+        self.vae._calls += 1
+        y = self.vae.forward_device(self.segments(inputs, b64, effnet_output), eps=eps, ctr=self.vae._calls)["y"]
+        return out_3d, (y[:, :16], y[:, 16:])
 
     def save_weights(self, path):
         self.vae.save_weights(path)

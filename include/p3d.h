@@ -528,6 +528,35 @@ int p3d_vae_destroy(p3d_vae* v);
 int64_t p3d_vae_lds_bytes(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent, int32_t n_dec,
                           const int32_t* dec_dims, int32_t out);
 
+/* The BONES filter (models.py:544-573 VAEBones, losses.py:113-156 loss_bones): the encoder and the
+ * reparametrisation of p3d_vae_create, the decoder dec_dims (ReLU) -> mag1 (16, ReLU) -> {mag2 (16),
+ * cos2 (48)}, both linear heads on mag1's output; out = 64 = [mag | cos], the layout of
+ * p3d_bones_from_joints.  (The reference also constructs a layer "cos1"; its output is overwritten
+ * before keras.Model is formed, so it is not part of the model and has no weights.)  The limits
+ * of p3d_vae_create apply, in > 256 is the wide form.  The parameter table ends
+ * "dec_f_<units>/...", "mag1/kernel", "mag1/bias", "mag2/...", "cos2/...".  Every p3d_vae_* call
+ * takes the handle; where a bones filter differs it is said at the call's declaration. */
+int p3d_vae_create_bones(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent, int32_t n_dec,
+                         const int32_t* dec_dims, int32_t max_batch, uint64_t seed, p3d_vae** v);
+/* p3d_vae_lds_bytes for a bones filter.  Host only. */
+int64_t p3d_vae_bones_lds_bytes(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent, int32_t n_dec,
+                                const int32_t* dec_dims);
+/* 0: p3d_vae_create's filter (ELBO), 1: a bones filter; -1 for a null handle. */
+int32_t p3d_vae_kind(const p3d_vae* v);
+
+/* joints [B, 48] float32 (hip-centred, joint k >= 1 in columns 3 (k - 1) ..) -> out64 [B, 64] =
+ * [bone lengths (16) | direction cosines (16 x 3)] over the bones
+ *   from 0 1 2 0 4 5 0 7 8  9  9 14 15  9 11 12
+ *   to   1 2 3 4 5 6 7 8 9 10 14 15 16 11 12 13   (bones.py:74-75).
+ * precise = 1 is bones.py:101-121 convert_to_bones (float64 arithmetic, one rounding to float32),
+ * precise = 0 bones.py:71-98 convert_to_bones_tf (float32 throughout, sum of squares left to
+ * right); sqrt and divide correctly rounded, no FMA contraction.  A zero-length bone gives NaN
+ * cosines.  B in 1 .. 2^20; asynchronous, capturable; argument errors answer without a GPU. */
+int p3d_bones_from_joints(const float* joints, int64_t B, int32_t precise, float* out64, void* stream);
+/* bones.py:124-153 convert_to_joints: bones64 [B, 64] -> joints_f64 [B, 48] float64, in bone order
+ * J[to] = J[from] + (double)(cos * mag), the product float32.  Same limits. */
+int p3d_bones_to_joints(const float* bones64, int64_t B, double* joints_f64, void* stream);
+
 /* Parameter table in Keras order and names (model.get_weights(), models.py:29-49):
  * "enc_h_<units>/kernel", "enc_h_<units>/bias", ..., "mean/kernel", "mean/bias",
  * "log_varianze/kernel", "log_varianze/bias", "dec_f_<units>/kernel", ..., "dec_f_out/bias".
@@ -548,23 +577,30 @@ int p3d_vae_params_updated(p3d_vae* v, void* stream);
  * -- tf.random.normal's own stream is not reproducible.  mean, log_var, z [B, latent] are
  * written when non-null; with a target [B, out], row_terms [B, 3] receives per row the mean
  * square likelihood, the KCS error (out == 48 only, else 0) and the KL divergence of
- * losses.py:29-32.  ctr = P3D_CTR_GLOBAL_STEP reads the device step counter. */
+ * losses.py:29-32.  ctr = P3D_CTR_GLOBAL_STEP reads the device step counter.
+ * Bones filter: y and target are [B, 64] = [mag | cos]; row_terms is [B, 4]: mean_16 (tm - pm)^2,
+ * 3 mean_48 (tc - pc)^2, the KL divergence, mean_16x16 |G(tc) - G(pc)| (losses.py:127-152). */
 int p3d_vae_forward(p3d_vae* v, const float* x, int64_t B, const float* eps, uint64_t ctr, float* y, float* mean,
                     float* log_var, float* z, const float* target, float* row_terms, void* stream);
 
 /* ELBO.compute_loss (losses.py:14-40): loss3_dev = [likef mean_B like, kcsf mean_B kcs,
  * dklf mean_B dkl] for factors = {likef, kcsf, dklf}; B <= max_batch.  kcsf must be 0 unless
- * out == 48 (P3D_ERR_ARG). */
+ * out == 48 (P3D_ERR_ARG).
+ * Bones filter: factors[4] = {mag, cos, dkl, ang}, t is [B, 64] and loss3_dev receives FOUR floats
+ * [MAG, COS, DKL, ANG] (losses.py:154). */
 int p3d_vae_loss(p3d_vae* v, const float* x, const float* t, int64_t B, const float* eps, uint64_t ctr,
                  const float* factors, float* loss3_dev, void* stream);
 /* The same plus tape.gradient of the three terms' sum (3d_pose_vae_filter.py:191-194) into the
  * gradient buffer; no optimizer.  Sums are associated by row index alone (16-row tiles in order
- * inside a 64-row block, blocks in order), so the gradient does not depend on the launch form. */
+ * inside a 64-row block, blocks in order), so the gradient does not depend on the launch form.
+ * Bones filter: factors[4] and a four-float loss as p3d_vae_loss; the gradient is that of the four
+ * terms' sum. */
 int p3d_vae_grad(p3d_vae* v, const float* x, const float* t, int64_t B, const float* eps, uint64_t ctr,
                  const float* factors, float* loss3_dev, void* stream);
 /* train_step_vae (3d_pose_vae_filter.py:188-196): loss, gradient and Keras Adam
  * (optimizer.apply_gradients; beta 0.9 / 0.999, epsilon 1e-7) with the device step counter as
- * the eps counter.  B <= 64 is ONE launch; larger batches add the block reduction + Adam launch. */
+ * the eps counter.  B <= 64 is ONE launch; larger batches add the block reduction + Adam launch.
+ * Bones filter: factors[4] and a four-float loss as p3d_vae_loss; the launches are the same. */
 int p3d_vae_train_step(p3d_vae* v, const float* x, const float* t, int64_t B, const float* eps,
                        const float* factors, float lr, float* loss3_dev, void* stream);
 /* Keras Adam over the gradient buffer as it stands (after p3d_vae_grad): the stand-alone form
@@ -603,7 +639,8 @@ int p3d_vae_cat_check(const p3d_vae_cat* cat, int32_t in, int64_t B);
 /* p3d_vae_forward / _loss / _grad / _train_step with the segments in place of x: the bits of the
  * plain call on the materialised concatenation.  They serve narrow filters too ([x2d | out_3d],
  * in = 80, is the reference's use_2d alone).  On a wide filter the plain calls are the
- * one-segment, no-index case of the same kernels. */
+ * one-segment, no-index case of the same kernels.
+ * Bones filter: factors[4], loss[4] and row_terms [B, 4] as at the plain calls. */
 int p3d_vae_forward_cat(p3d_vae* v, const p3d_vae_cat* cat, int64_t B, const float* eps, uint64_t ctr, float* y,
                         float* mean, float* log_var, float* z, const float* target, float* row_terms, void* stream);
 int p3d_vae_loss_cat(p3d_vae* v, const p3d_vae_cat* cat, const float* t, int64_t B, const float* eps, uint64_t ctr,
@@ -626,7 +663,8 @@ int p3d_vae_train_step_cat(p3d_vae* v, const p3d_vae_cat* cat, const float* t, i
  * groups across calls so that a stream can be filtered in chunks: started[s] == 0 primes the
  * buffer from the chunk's first frame and sets started[s] = 1.  Empty sequences write nothing
  * (their seq_err is 0) and leave their state untouched.  Asynchronous, capturable; all pointers
- * are device pointers, the float arrays 16-byte aligned.  S and N in 1 .. 2^20. */
+ * are device pointers, the float arrays 16-byte aligned.  S and N in 1 .. 2^20.
+ * A bones filter has no sequence form: P3D_ERR_ARG. */
 int p3d_vae_seq_filter(p3d_vae* v,
         const float* pred,          /* [N, out] lifter outputs, sequences concatenated          */
         const int64_t* seq_off,     /* device, [S + 1], non-decreasing, seq_off[0] = 0, [S] = N */
