@@ -6,7 +6,9 @@ train() (:158-280) trains it as a denoiser on sliding windows of the 3D sequence
 batch -- without the plots, gen_sample_img, tqdm and the TF2 checkpoints.  Per epoch the shuffled
 windows are gathered on the device with a torch index and noised ONCE over the whole epoch on the
 host; the reference draws its noise batch by batch, so the np.random stream differs and the noise's
-distribution does not.
+distribution does not.  With --device_noise the epoch's windows are instead read in place and noised
+on the GPU by one data_handler.add_noise_device call (p3d_vae_add_noise, keyed by --seed and the
+epoch): nothing is copied to the host and np.random draws only the epoch's permutation.
 
 evaluate() (:285-361) runs the filter the way it is used: as a recurrence over every test sequence
 on top of the frozen lifter, each frame's refined pose written back into the buffer that feeds the
@@ -89,8 +91,13 @@ def train(argv=None, read_from_config=False):
     for epoch in range(1, f.epochs + 1):
         print("\nStarting epoch:", epoch)
         order = torch.from_numpy(np.random.permutation(len(st_tr))).to(dev)
-        X, Y = gather(fr_tr, st_tr[order])
-        X = torch.from_numpy(data_handler.add_noise(X.cpu().numpy(), f.noise_3d)).to(dev)
+        if f.device_noise and len(st_tr):      # the windows read in place and noised in one launch: no host copy
+            so = st_tr[order]
+            X = data_handler.add_noise_device(fr_tr, f.noise_3d, starts=so, width=SEQ_LEN * size, seed=f.seed, ctr=epoch)
+            Y = fr_tr[so + (SEQ_LEN - 1)]
+        else:
+            X, Y = gather(fr_tr, st_tr[order])
+            X = torch.from_numpy(data_handler.add_noise(X.cpu().numpy(), f.noise_3d)).to(dev)
         step_losses = torch.zeros((max(nb_tr, 1), 3), dtype=torch.float32, device=dev)
         for step in range(nb_tr):
             model.train_step_device(X[step * B:(step + 1) * B], Y[step * B:(step + 1) * B], _factors(f),

@@ -150,6 +150,10 @@ SIGNATURES = [
     ("p3d_vae_get_step", c_int32, [c_void_p, POINTER(c_int64), POINTER(c_float), POINTER(c_float)]),
     ("p3d_vae_set_step", c_int32, [c_void_p, c_int64, c_float, c_float]),
     ("p3d_vae_eps", c_int32, [c_uint64, c_uint64, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
+    ("p3d_vae_add_noise", c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int64, c_uint64, c_uint64,
+                                    c_int64, c_float, c_float, c_float, c_void_p, c_void_p]),
+    ("p3d_vae_add_noise_thr", c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int64, c_uint64, c_uint64,
+                                        c_int64, c_float, c_float, c_float, c_uint64, c_void_p, c_void_p]),
     ("p3d_vae_workspace", c_int64, [c_void_p, c_int64]),
     ("p3d_vae_cat_check", c_int32, [POINTER(P3DVaeCat), c_int32, c_int64]),
     ("p3d_vae_forward_cat", c_int32, [c_void_p, POINTER(P3DVaeCat), c_int64, c_void_p, c_uint64, c_void_p, c_void_p,

@@ -43,6 +43,7 @@
 #include "p3d_bones.h"
 #include "p3d_vae_seq.h"
 #include "p3d_vae_wide.h"
+#include "p3d_vae_noise.h"
 
 // =====================================================================================
 // host side
@@ -3274,6 +3275,56 @@ extern "C" int p3d_vae_eps(uint64_t seed, uint64_t ctr, int64_t row0, int64_t B,
                      row0, B, (int)latent, out);
   LAUNCH_CHECK("k_vae_eps");
   return P3D_OK;
+}
+
+namespace {
+int vae_add_noise(const float* src, int64_t rows, int32_t d, const int64_t* starts, int32_t width, int64_t B,
+                  uint64_t seed, uint64_t ctr, int64_t row0, float noise, float offset, float joint_scale,
+                  uint64_t thr, float* out, void* stream, const char* what) {
+  const std::string w(what);
+  if (!src || !out) return fail(P3D_ERR_ARG, w + ": null argument");
+  if (width < 12 || width > P3D_NOISE_MAX_WIDTH || width % 12 != 0)
+    return fail(P3D_ERR_ARG, w + ": width must be a multiple of 12 in 12 .. 240");
+  if (d < 4 || d % 4 != 0) return fail(P3D_ERR_ARG, w + ": d must be a positive multiple of 4");
+  if (width % d != 0) return fail(P3D_ERR_ARG, w + ": width must be a multiple of d");
+  if (B < 1 || B > (1 << 20)) return fail(P3D_ERR_ARG, w + ": B must be in 1 .. 2^20");
+  if (!aligned16(src) || !aligned16(out)) return fail(P3D_ERR_ARG, w + ": src and out must be 16-byte aligned");
+  if (((uintptr_t)starts & 7) != 0) return fail(P3D_ERR_ARG, w + ": starts must be 8-byte aligned");
+  const uintptr_t s0 = (uintptr_t)src, o0 = (uintptr_t)out;
+  const bool overlap = rows > 0 && s0 < o0 + (uintptr_t)B * width * 4 && o0 < s0 + (uintptr_t)rows * d * 4;
+  if (starts) {
+    if (rows < width / d) return fail(P3D_ERR_ARG, w + ": the table has fewer rows than a window");
+    if (overlap) return fail(P3D_ERR_ARG, w + ": in the window form out may not overlap src");
+  } else {
+    if (width != d) return fail(P3D_ERR_ARG, w + ": without starts width must equal d");
+    if (rows < B) return fail(P3D_ERR_ARG, w + ": without starts the table needs at least B rows");
+    if (overlap && src != out) return fail(P3D_ERR_ARG, w + ": out may be src itself, not another overlapping range");
+  }
+  NoiseArgs a;
+  a.src = src; a.rows = rows; a.starts = starts; a.B = B; a.row0 = row0; a.seed = seed; a.ctr = ctr; a.thr = thr;
+  a.noise = noise; a.offset = offset; a.joint_scale = joint_scale; a.d = d; a.width = width;
+  const uint64_t c4n = (uint64_t)(width / 4);
+  a.magic = (uint32_t)(((1ull << 32) + c4n - 1) / c4n);
+  a.out = out;
+  hipLaunchKernelGGL(k_vae_noise, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  LAUNCH_CHECK("k_vae_noise");
+  return P3D_OK;
+}
+}  // namespace
+
+extern "C" int p3d_vae_add_noise(const float* src, int64_t rows, int32_t d, const int64_t* starts, int32_t width,
+                                 int64_t B, uint64_t seed, uint64_t ctr, int64_t row0, float noise, float offset,
+                                 float joint_scale, float* out, void* stream) {
+  return vae_add_noise(src, rows, d, starts, width, B, seed, ctr, row0, noise, offset, joint_scale,
+                       P3D_NOISE_THRESHOLD, out, stream, "p3d_vae_add_noise");
+}
+
+extern "C" int p3d_vae_add_noise_thr(const float* src, int64_t rows, int32_t d, const int64_t* starts, int32_t width,
+                                     int64_t B, uint64_t seed, uint64_t ctr, int64_t row0, float noise, float offset,
+                                     float joint_scale, uint64_t threshold, float* out, void* stream) {
+  if (threshold > (1ull << 32)) return fail(P3D_ERR_ARG, "p3d_vae_add_noise_thr: threshold must be in 0 .. 2^32");
+  return vae_add_noise(src, rows, d, starts, width, B, seed, ctr, row0, noise, offset, joint_scale, threshold, out,
+                       stream, "p3d_vae_add_noise_thr");
 }
 
 extern "C" int64_t p3d_vae_seq_lds_bytes(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent,

@@ -86,9 +86,11 @@ __device__ __forceinline__ int vae_par(int a) { return (int)((P3D_VAE_PAR >> (4 
 
 // Four standard normals of eps row `row`, columns 4 c4 .. 4 c4 + 3: one Philox4x32-10 block keyed
 // (seed, ctr, site, row, c4) through TF's Box-Muller (random_distributions.h BoxMullerFloat).
-__device__ __forceinline__ void vae_eps4(uint64_t seed, uint64_t ctr, int64_t row, int c4, float e[4]) {
+// vae_eps4_site is the construction over any site: the noise stream (p3d_vae_noise.h) draws from it.
+__device__ __forceinline__ void vae_eps4_site(uint64_t seed, uint64_t ctr, uint32_t site, int64_t row, int c4,
+                                              float e[4]) {
 #pragma clang fp contract(off)
-  const uint4 w = p3d_philox(make_uint4((uint32_t)row, (uint32_t)c4, (uint32_t)P3D_VAE_SITE, (uint32_t)ctr),
+  const uint4 w = p3d_philox(make_uint4((uint32_t)row, (uint32_t)c4, site, (uint32_t)ctr),
                              (uint32_t)seed, (uint32_t)(seed >> 32));
   const uint32_t xs[4] = {w.x, w.y, w.z, w.w};
 #pragma unroll
@@ -101,6 +103,9 @@ __device__ __forceinline__ void vae_eps4(uint64_t seed, uint64_t ctr, int64_t ro
     e[2 * h] = sinf(ang) * r;
     e[2 * h + 1] = cosf(ang) * r;
   }
+}
+__device__ __forceinline__ void vae_eps4(uint64_t seed, uint64_t ctr, int64_t row, int c4, float e[4]) {
+  vae_eps4_site(seed, ctr, (uint32_t)P3D_VAE_SITE, row, c4, e);
 }
 
 __global__ __launch_bounds__(256) void k_vae_eps(uint64_t seed, uint64_t ctr, int64_t row0, int64_t B, int latent,

@@ -43,6 +43,8 @@ def build_parser():
     p.add_argument("--cfg_file", type=str, default="src/train.yml",
                    help="Config file, the values passed through args are remplaced by the specified in the file")
     p.add_argument("--sample", action='store_true', default=False, help="Set to True for sampling.")
+    p.add_argument("--noised_sample", action='store_true', default=False,
+                   help="Set to True for generate a sample of data with noise.")
     p.add_argument("--load", type=int, default=0, help="Try to load a previous checkpoint.")
     p.add_argument("--verbose", type=int, default=2, help="0:Error, 1:Warning, 2:INFO*(default), 3:debug")
     p.add_argument("--noise_3d", type=float, nargs=2, default=[1, 1],
@@ -62,7 +64,10 @@ def build_parser():
     p.add_argument("--num_layers", type=int, default=2, help="Lifter: number of two_linear blocks")
     p.add_argument("--lifter_dir", type=str, default=None,
                    help="Lifter: the directory holding checkpoint-<load> (a predict_3dpose.train run's directory)")
-    p.add_argument("--seed", type=int, default=0, help="Weight / eps seed")
+    p.add_argument("--seed", type=int, default=0, help="Weight / eps / device-noise seed")
+    # build-specific: 3d_pose_vae_filter_kin.py draws an epoch's noise on the device (data_handler.add_noise_device)
+    p.add_argument("--device_noise", action='store_true', default=False,
+                   help="Temporal filter: noise an epoch's windows on the GPU instead of through the host")
     return p
 
 

@@ -616,6 +616,38 @@ int p3d_vae_set_step(p3d_vae* v, int64_t step, float beta1_power, float beta2_po
 /* Rows row0 .. row0 + B - 1 of the eps stream (tf.random.normal of models.py:70) as
  * p3d_vae_forward draws them: out [B, latent], latent a multiple of 4. */
 int p3d_vae_eps(uint64_t seed, uint64_t ctr, int64_t row0, int64_t B, int32_t latent, float* out, void* stream);
+/* The noise the filters are trained to remove (data_handler.py:48-84 add_noise) as a counter-based
+ * stream, one launch (k_vae_noise, csrc/p3d_vae_noise.h).  Output row r is the `width` contiguous
+ * floats of the table src [rows, d] that begin at row starts[r] (width = k d: a window of k frames
+ * read in place; the device clamps starts[r] into [0, rows - k]); with starts null, width == d and
+ * output row r is row r of src.  With g = row0 + r (its low 32 bits, and ctr's):
+ *
+ *   element normals  columns 4c .. 4c+3: p3d_vae_eps's construction over the Philox counter
+ *                    (g, c, P3D_NOISE_SITE, ctr), key seed
+ *   row block A      counter (g, 0, P3D_NOISE_ROW_SITE, ctr): the row is noised iff
+ *                    A.x >= 0xB103AF11 = floor(Phi(0.5) 2^32) (30.85 % of the rows); the chosen
+ *                    column is jc = ((uint64_t)A.y * width) >> 32, its joint starts at jid = jc - jc % 3
+ *   row block B      counter (g, 1, P3D_NOISE_ROW_SITE, ctr) through the same Box-Muller: its first
+ *                    three normals j0, j1, j2
+ *
+ * A row that is not noised is copied bit for bit.  A noised row gets, in float32 with every
+ * operation rounded once, v[c] = x[c] + (e[c] * noise + offset) on every column and then
+ * v[jid + k] = v[jid + k] + j_k * joint_scale for k = 0, 1, 2.
+ * width a multiple of 12 in 12 .. 240 and of d, d a multiple of 4, 1 <= B <= 2^20, src and out
+ * 16-byte aligned, rows >= B without starts.  Without starts out may be src (in place); in the
+ * window form out may not overlap src.  Asynchronous, capturable.
+ * P3D_NOISE_SITE = 0x4E4F49 and P3D_NOISE_ROW_SITE = 0x4E4F52 (the eps stream's site is 0x564145,
+ * the dropout sites are < 64). */
+int p3d_vae_add_noise(const float* src, int64_t rows, int32_t d,      /* table [rows, d] float32          */
+                      const int64_t* starts, int32_t width, int64_t B,/* null: row r is src row r         */
+                      uint64_t seed, uint64_t ctr, int64_t row0,
+                      float noise, float offset, float joint_scale,
+                      float* out /* [B, width] */, void* stream);
+/* The same with the threshold word given (0 .. 2^32: 0 noises every row, 2^32 none).  For
+ * measurements of what the clean rows' skipped Box-Muller saves; training code calls the above. */
+int p3d_vae_add_noise_thr(const float* src, int64_t rows, int32_t d, const int64_t* starts, int32_t width,
+                          int64_t B, uint64_t seed, uint64_t ctr, int64_t row0, float noise, float offset,
+                          float joint_scale, uint64_t threshold, float* out, void* stream);
 /* Bytes of the library-owned workspace a gradient over B rows uses (per-block partials; a wide
  * filter: the partials of the layers behind layer 0, plus h0 and dz0, 2 B enc_dims[0] floats). */
 int64_t p3d_vae_workspace(const p3d_vae* v, int64_t B);
