@@ -44,6 +44,7 @@
 #include "p3d_vae_seq.h"
 #include "p3d_vae_wide.h"
 #include "p3d_vae_noise.h"
+#include "p3d_vae_dec.h"
 
 // =====================================================================================
 // host side
@@ -2635,6 +2636,12 @@ struct p3d_vae {
   int wide = 0, in = 0, n0 = 0, P0 = 0, Ptot = 0;
   std::vector<VaeTensor> tensors;       // the full parameter table (flat offsets into the master buffers)
   int64_t h0_off = 0, dz0_off = 0;      // float offsets of h0 and dz0 in the workspace
+  // the decoder on its own (k_vae_dec; kernels in p3d_vae_dec.h): the decoder-only descriptor, the
+  // float offset of its parameters in the packed copy, its dynamic LDS and its workgroups per CU
+  VaeDesc dec{};
+  VaeDesc* d_dec = nullptr;
+  int dec_base = 0, dec_wgs = 0;
+  size_t dec_lds = 0;
 };
 
 namespace {
@@ -2771,6 +2778,38 @@ size_t vae_seq_layout(const VaeDesc& d, int& xoff, int& toff, int& ldt, int& mof
   toff = act; act += 16 * ldt;
   moff = act; act += 16 * 2 + 16;   // (act stays a multiple of 4: the int64 offsets are aligned)
   return sizeof(float) * ((size_t)d.Ppk + (size_t)act);
+}
+
+// The decoder-only descriptor of a laid-out filter: the packed range of layers head + 1 .. nl - 1
+// (`base` floats into the packed copy; vae_layout packs the layers in order, which is checked here)
+// with wpk / bpk rebased to it, and a wave's area shrunk to the z tile and the decoder's
+// activations.  Returns the dynamic LDS bytes of k_vae_dec, 0 if the range is not contiguous.
+size_t vae_dec_layout(const VaeDesc& full, VaeDesc& dd, int& base) {
+  dd = full;
+  base = full.L[full.head + 1].wpk;
+  int pk = base, act = 0;
+  dd.zbuf = act; act += 16 * dd.ldz;
+  dd.ebuf = dd.bt = dd.xbuf = -1;
+  for (int l = 0; l <= full.head; ++l) dd.L[l] = VaeLayer{};
+  for (int l = full.head + 1; l < full.nl; ++l) {
+    VaeLayer& L = dd.L[l];
+    if (L.wpk != pk || L.bpk != pk + L.K * L.ld) return 0;
+    pk = L.bpk + L.Np;
+    L.wpk -= base; L.bpk -= base;
+    L.ain = l == full.head + 1 ? dd.zbuf : dd.L[l - 1].aout;
+    L.lda = l == full.head + 1 ? dd.ldz : dd.L[l - 1].ldo;
+    L.aout = act; act += 16 * L.ldo;
+  }
+  if ((pk + 3) / 4 * 4 != full.Ppk || base % 4 != 0) return 0;
+  dd.Ppk = full.Ppk - base;
+  dd.act = (act + 3) / 4 * 4;
+  return sizeof(float) * ((size_t)dd.Ppk + 4 * (size_t)dd.act);
+}
+
+// workgroups of k_vae_dec per CU: as many as the CU's LDS holds, four at the most
+int vae_dec_fit(size_t lds) {
+  const int fit = (int)(P3D_VAE_LDS_LIMIT / (lds ? lds : 1));
+  return fit < 1 ? 1 : (fit > 4 ? 4 : fit);
 }
 
 int vae_check_call(const p3d_vae* v, const void* x, int64_t B, const char* what) {
@@ -2954,6 +2993,20 @@ extern "C" int64_t p3d_vae_lds_bytes(int32_t in, int32_t n_enc, const int32_t* e
                                   out);
 }
 
+extern "C" int64_t p3d_vae_dec_lds_bytes(int32_t latent, int32_t n_dec, const int32_t* dec_dims, int32_t out,
+                                         int32_t bones) {
+  const int32_t enc[1] = {8};   // (the decoder's layout does not depend on the encoder)
+  if (bones != 0 && bones != 1) return 0;
+  if (vae_check_shape(8, 1, enc, latent, n_dec, dec_dims, bones ? 64 : out)) return 0;
+  VaeDesc d, dd;
+  std::vector<std::string> names;
+  int base;
+  vae_layout(d, names, bones ? P3D_VAE_KIND_BONES : P3D_VAE_KIND_ELBO, 8, 1, enc, latent, n_dec, dec_dims,
+             bones ? 64 : out, 4, 1);
+  const size_t lds = vae_dec_layout(d, dd, base);
+  return lds <= P3D_VAE_LDS_LIMIT ? (int64_t)lds : 0;
+}
+
 extern "C" int64_t p3d_vae_bones_lds_bytes(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent,
                                            int32_t n_dec, const int32_t* dec_dims) {
   if (vae_check_shape(in, n_enc, enc_dims, latent, n_dec, dec_dims, 64)) return 0;
@@ -2983,6 +3036,12 @@ int vae_create(int kind, int32_t in, int32_t n_enc, const int32_t* enc_dims, int
     return fail(P3D_ERR_ARG, "p3d_vae_create: parameters and working space need " + std::to_string(need) +
                                  " bytes of LDS, a workgroup has " + std::to_string(P3D_VAE_LDS_LIMIT));
   }
+  v->dec_lds = vae_dec_layout(v->desc, v->dec, v->dec_base);   // (host only: the decoder's range of the packed copy)
+  if (!v->dec_lds || v->dec_lds > v->lds) {
+    delete v;
+    return fail(P3D_ERR_STATE, "p3d_vae_create: the decoder's parameters are not one range of the packed copy");
+  }
+  v->dec_wgs = vae_dec_fit(v->dec_lds);
   for (size_t i = 0; i < v->names.size(); ++i)
     for (size_t j = 0; j < i; ++j)
       if (v->names[i] == v->names[j]) {   // keras: "All layers added to a Model must have unique names"
@@ -3033,6 +3092,11 @@ int vae_create(int kind, int32_t in, int32_t n_enc, const int32_t* enc_dims, int
     if ((e = hipMemcpy(v->pkidx, idx.data(), sizeof(int) * idx.size(), hipMemcpyHostToDevice)) != hipSuccess)
       return bail(e, "hipMemcpy");
   }
+  if ((e = hipMalloc((void**)&v->d_dec, sizeof(VaeDesc))) != hipSuccess) return bail(e, "hipMalloc");
+  if ((e = hipMemcpy(v->d_dec, &v->dec, sizeof(VaeDesc), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
+  for (const void* k : {(const void*)k_vae_dec, (const void*)k_vae_bones_dec})
+    if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->dec_lds)) != hipSuccess)
+      return bail(e, "hipFuncSetAttribute(k_vae_dec)");
   if ((e = hipMalloc((void**)&v->st, sizeof(VaeState))) != hipSuccess) return bail(e, "hipMalloc");
   const VaeState s0{0, 0.9f, 0.999f, 0.0f, {0, 0, 0}};
   if ((e = hipMemcpy(v->st, &s0, sizeof(VaeState), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
@@ -3098,7 +3162,7 @@ extern "C" int p3d_bones_to_joints(const float* bones64, int64_t B, double* join
 
 extern "C" int p3d_vae_destroy(p3d_vae* v) {
   if (!v) return P3D_OK;
-  void* bufs[] = {v->params, v->grads, v->am, v->av, v->pk, v->ws, v->d_desc, v->st, v->pkidx};
+  void* bufs[] = {v->params, v->grads, v->am, v->av, v->pk, v->ws, v->d_desc, v->st, v->pkidx, v->d_dec};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   delete v;
@@ -3162,6 +3226,37 @@ extern "C" int p3d_vae_forward(p3d_vae* v, const float* x, int64_t B, const floa
                                void* stream) {
   if (int rc = vae_check_call(v, x, B, "p3d_vae_forward")) return rc;
   return vae_forward(v, x, nullptr, B, eps, ctr, y, mean, log_var, z, target, row_terms, stream, "p3d_vae_forward");
+}
+
+// The errors that need no filter answer first (and without a GPU).
+extern "C" int p3d_vae_decode(p3d_vae* v, const float* z, int64_t B, uint64_t ctr, int64_t row0, float* y,
+                              float* z_out, void* stream) {
+  if (!y) return fail(P3D_ERR_ARG, "p3d_vae_decode: y is null");
+  if (B < 1 || B > (1 << 20)) return fail(P3D_ERR_ARG, "p3d_vae_decode: B must be in 1 .. 2^20");
+  if (z && z_out) return fail(P3D_ERR_ARG, "p3d_vae_decode: z_out receives the drawn z: give z or z_out, not both");
+  if (row0 < 0) return fail(P3D_ERR_ARG, "p3d_vae_decode: row0 must be >= 0");
+  if (ctr == P3D_CTR_GLOBAL_STEP)
+    return fail(P3D_ERR_ARG, "p3d_vae_decode: the prior stream has no device counter (ctr may not be P3D_CTR_GLOBAL_STEP)");
+  if (!v) return fail(P3D_ERR_ARG, "p3d_vae_decode: null handle");
+  VaeDecArgs a{};
+  a.desc = v->d_dec; a.pk = v->pk + v->dec_base; a.z = z; a.B = B; a.row0 = row0;
+  a.seed = v->seed; a.ctr = ctr; a.y = y; a.z_out = z_out;
+  const int64_t nwg = (B + 63) / 64, cap = (int64_t)v->cus * v->dec_wgs;
+  const int grid = (int)(nwg < cap ? nwg : cap);
+  hipLaunchKernelGGL(v->kind == P3D_VAE_KIND_BONES ? k_vae_bones_dec : k_vae_dec, dim3(grid), dim3(256), v->dec_lds,
+                     (hipStream_t)stream, a);
+  LAUNCH_CHECK("k_vae_dec");
+  return P3D_OK;
+}
+
+extern "C" int p3d_vae_dec_set_grid(p3d_vae* v, int32_t wgs_per_cu) {
+  if (!v) return fail(P3D_ERR_ARG, "p3d_vae_dec_set_grid: null handle");
+  const int fit = (int)(P3D_VAE_LDS_LIMIT / v->dec_lds);
+  if (wgs_per_cu < 0 || wgs_per_cu > (fit < 16 ? fit : 16))
+    return fail(P3D_ERR_ARG, "p3d_vae_dec_set_grid: workgroups per CU must be 0 (the default) or 1 .. " +
+                                 std::to_string(fit < 16 ? fit : 16) + " (what a CU's LDS holds)");
+  v->dec_wgs = wgs_per_cu ? wgs_per_cu : vae_dec_fit(v->dec_lds);
+  return P3D_OK;
 }
 
 extern "C" int p3d_vae_loss(p3d_vae* v, const float* x, const float* t, int64_t B, const float* eps, uint64_t ctr,

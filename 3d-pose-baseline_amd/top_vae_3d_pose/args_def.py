@@ -68,6 +68,10 @@ def build_parser():
     # build-specific: 3d_pose_vae_filter_kin.py draws an epoch's noise on the device (data_handler.add_noise_device)
     p.add_argument("--device_noise", action='store_true', default=False,
                    help="Temporal filter: noise an epoch's windows on the GPU instead of through the host")
+    # build-specific: the numbers behind gen_sample_img's picture (top_vae_3d_pose/samples.py)
+    p.add_argument("--samples_dir", type=str, default="",
+                   help="vae_filter.py: write each epoch's sample set (real, noised, predicted poses) to "
+                        "DIR/samples_<epoch>.npz; empty (the default): off")
     return p
 
 

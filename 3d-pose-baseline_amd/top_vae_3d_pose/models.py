@@ -391,10 +391,44 @@ class VAE(object):
         eps = self.eps_device(mean.shape[0], ctr=self._calls)
         return eps * self.torch.exp(log_var * 0.5) + mean
 
+    MAX_LAUNCH_ROWS = 1 << 20   # the library's bound on one call's rows
+
     def decode(self, z):
-        """models.py:74-76 -- the decoder alone is not a library entry point."""
-        raise NotImplementedError("VAE.decode on its own is not built: the filter runs encode, reparametrize and "
-                                  "decode in one launch (call the model, or forward_device for z and y together)")
+        """The decoder alone (models.py:74-76): y [B, out] from z [B, latent] in one k_vae_dec launch,
+        bit-identical to the y forward_device gives for the same z."""
+        z = self._dev(z, self.latent_dim, "z")
+        B = z.shape[0]
+        y = self.torch.empty((B, self.output_size), dtype=self.torch.float32, device=self.device)
+        check(lib().p3d_vae_decode(self._h, ptr(z), B, 0, 0, ptr(y), None, self.stream()), "p3d_vae_decode")
+        return y
+
+    def sample(self, n, ctr=0, row0=0, want=("y",)):
+        """n poses from the prior: z ~ N(0, I) drawn inside the decoder's launch from the library's
+        prior stream (keyed by the model's seed, ctr, the global row row0 + r and the column) and
+        decoded, with no input tensor.  Returns a dict with 'y' [n, out] and, if asked, 'z'
+        [n, latent].  More than 2^20 rows go out as several launches with row0 advanced: the
+        stream is keyed by the global row, so the split does not show."""
+        torch = self.torch
+        n, row0 = int(n), int(row0)
+        if n < 1:
+            raise ValueError("sample: n must be at least 1, got %d" % n)
+        unknown = [k for k in want if k not in ("y", "z")]
+        if unknown:
+            raise ValueError("sample: unknown outputs %s" % unknown)
+        y = torch.empty((n, self.output_size), dtype=torch.float32, device=self.device)
+        z = torch.empty((n, self.latent_dim), dtype=torch.float32, device=self.device) if "z" in want else None
+        for r in range(0, n, self.MAX_LAUNCH_ROWS):
+            b = min(self.MAX_LAUNCH_ROWS, n - r)
+            check(lib().p3d_vae_decode(self._h, None, b, int(ctr), row0 + r, ptr(y[r:r + b]),
+                                       None if z is None else ptr(z[r:r + b]), self.stream()), "p3d_vae_decode")
+        out = {"y": y}
+        if z is not None:
+            out["z"] = z
+        return out
+
+    def set_dec_grid(self, wgs_per_cu):
+        """Workgroups of the decoder's launch per CU (0: the library's default).  Same bits either way."""
+        check(lib().p3d_vae_dec_set_grid(self._h, int(wgs_per_cu)), "p3d_vae_dec_set_grid")
 
     def __call__(self, inputs, training=False, eps=None):
         self._calls += 1
@@ -436,6 +470,17 @@ class VAEBones(VAE):
         self._calls += 1
         y = self.forward_device(inputs, eps=eps, ctr=self._calls)["y"]
         return y[:, :16], y[:, 16:]
+
+    def decode(self, z):
+        """(mag, cos) views of the decoder's [B, 64] output; bones.convert_to_joints turns them into joints."""
+        y = super(VAEBones, self).decode(z)
+        return y[:, :16], y[:, 16:]
+
+    def sample(self, n, ctr=0, row0=0, want=("y",)):
+        """VAE.sample with 'y' as the (mag, cos) views of one [n, 64] tensor."""
+        out = super(VAEBones, self).sample(n, ctr=ctr, row0=row0, want=want)
+        out["y"] = (out["y"][:, :16], out["y"][:, 16:])
+        return out
 
 
 class Pose3DVae(object):

@@ -1,16 +1,17 @@
 """Train the stand-alone VAE denoiser (src/vae_filter.py): a 48 -> 48 VAE that reads a 3D pose
 under data_handler's noise and returns the clean one.
 
-train() is the reference's epoch loop (:136-218) without the plots, gen_sample_img and the TF2
-checkpoints.  All 3D poses are joined, shuffled and split 80/20 (data_handler.load_3d_data) and live
-on the device; both halves are noised there (data_handler.Dataset, p3d_vae_add_noise) and re-noised
+train() is the reference's epoch loop (:136-218) without the plots and the TF2 checkpoints; with
+--samples_dir DIR it writes, where the reference calls gen_sample_img (:198-200), the numbers behind
+that picture to DIR/samples_<epoch>.npz (top_vae_3d_pose/samples.py).  All 3D poses are joined,
+shuffled and split 80/20 (data_handler.load_3d_data) and live on the device; both halves are noised there (data_handler.Dataset, p3d_vae_add_noise) and re-noised
 after every epoch, so an epoch moves no data between host and device: a batch is two device gathers
 and one p3d_vae_train_step launch.
 
 The reference's script is stale against its own package: it reads ``FLAGS.vae_dim`` and passes
 ``inter_dim=`` to a VAE that takes ``enc_dim`` / ``dec_dim``.  Here the shape comes from
 --enc_dim / --latent_dim / --dec_dim, as in the other drivers.  --noised_sample and --sample are
-matplotlib visualisation and raise NotImplementedError.
+matplotlib visualisation and raise NotImplementedError (--samples_dir gives their numbers).
 
     python vae_filter.py --camera_frame --epochs 20 --cfg_file train.yml
 """
@@ -20,7 +21,7 @@ import os
 import sys
 
 import predict_3dpose
-from top_vae_3d_pose import data_handler, losses, models
+from top_vae_3d_pose import data_handler, losses, models, samples
 from top_vae_3d_pose.args_def import ENVIRON as ENV
 
 
@@ -46,9 +47,11 @@ def train(argv=None, read_from_config=False):
     import torch
     f = ENV.setup(read_from_config=read_from_config, argv=argv)
     if f.noised_sample:
-        raise NotImplementedError("--noised_sample (gen_sample_img) is matplotlib visualisation, not built")
+        raise NotImplementedError("--noised_sample (gen_sample_img) is matplotlib visualisation, not built; "
+                                  "--samples_dir DIR writes the sample sets it would draw")
     if f.sample:
-        raise NotImplementedError("--sample (gen_sample_img) is matplotlib visualisation, not built")
+        raise NotImplementedError("--sample (gen_sample_img) is matplotlib visualisation, not built; "
+                                  "--samples_dir DIR writes the sample sets it would draw")
     base = _base()
     optimizer = base.get_optimizer()
     d = predict_3dpose.load_data(base.lifter_flags(f))
@@ -64,6 +67,11 @@ def train(argv=None, read_from_config=False):
     dev = model.device
     factors = (f.likelihood_factor, f.kcs_factor, f.dkl_factor)
     hist = {k: [] for k in ("loss_train", "loss_test", "error_pred", "error_noised")}
+    idx = None
+    if f.samples_dir:   # Indexes for sampling (:157): one draw, before the first epoch
+        import numpy as np
+        os.makedirs(f.samples_dir, exist_ok=True)
+        idx = np.random.choice(data_test.shape[0], samples.NSAMPLES, replace=False)
     for epoch in range(1, f.epochs + 1):
         print("\nStarting epoch:", epoch)
         nb = len(data_train)
@@ -87,6 +95,11 @@ def train(argv=None, read_from_config=False):
         print('Epoch: {}, Test set ELBO: {}'.format(epoch, hist["loss_test"][-1]))
         print('Error real vs noised:', hist["error_noised"][-1])
         print('Error real vs pred:', hist["error_pred"][-1])
+        if idx is not None:
+            print('\nSaving samples...')
+            meta = data_test.metadata
+            samples.gen_samples(model, data_test.data, data_test.data_noised, meta.mean, meta.std, meta.dim_ignored,
+                                idx=idx, path=samples.sample_path(f.samples_dir, epoch))
         # Reset data for next epoch
         data_train.on_epoch_end(new_noise=True)
         data_test.on_epoch_end(new_noise=True)

@@ -583,7 +583,32 @@ int p3d_vae_params_updated(p3d_vae* v, void* stream);
 int p3d_vae_forward(p3d_vae* v, const float* x, int64_t B, const float* eps, uint64_t ctr, float* y, float* mean,
                     float* log_var, float* z, const float* target, float* row_terms, void* stream);
 
-/* ELBO.compute_loss (losses.py:14-40): loss3_dev = [likef mean_B like, kcsf mean_B kcs,
+/* VAE.decode (models.py:74-76): y [B, out] from z [B, latent]; or, z null, from the prior stream
+ * (seed, ctr, P3D_VAE_PRIOR_SITE, row0 + r, c4), written to z_out when non-null.
+ * One launch (k_vae_dec, csrc/p3d_vae_dec.h) that holds only the decoder's parameters in LDS and
+ * runs the forward's own layer arithmetic in the forward's order: y is bit-identical to the y
+ * p3d_vae_forward writes for the same z, NaN and Inf included.  Works on every filter kind (a bones
+ * filter: y is [B, 64] = [mag | cos]; a wide filter: the decoder behind its core), for any
+ * 1 <= B <= 2^20 whatever max_batch is: no workspace is used.  Asynchronous, capturable.
+ * The prior stream: columns 4c .. 4c+3 of row r are p3d_vae_eps's construction (one Philox4x32-10
+ * block through TF's Box-Muller) over the counter (g, c, P3D_VAE_PRIOR_SITE, ctr), key seed, with
+ * g = row0 + r (its low 32 bits, and ctr's) and P3D_VAE_PRIOR_SITE = 0x505249 -- a site of its own
+ * (eps: 0x564145, noise: 0x4E4F49 / 0x4E4F52, dropout: < 64), so a sample is never the eps a
+ * training step draws at the same (seed, ctr, row).  Rows are keyed by g alone: a call over rows
+ * row0 .. row0 + B - 1 gives those rows of one longer call.
+ * P3D_ERR_ARG ("p3d_vae_decode: ..."), without touching the GPU: a null handle, a null y, B out of
+ * range, z and z_out both given, row0 < 0, ctr == P3D_CTR_GLOBAL_STEP. */
+int p3d_vae_decode(p3d_vae* v, const float* z, int64_t B, uint64_t ctr, int64_t row0,
+                   float* y, float* z_out, void* stream);
+/* Dynamic LDS bytes of the decoder kernels for this shape (host only; 0 for a refused shape): the
+ * decoder's packed parameters and four z-and-activation tiles, with the packed rows staggered as
+ * p3d_vae_create's first layout does (a filter that only fits unstaggered uses less). */
+int64_t p3d_vae_dec_lds_bytes(int32_t latent, int32_t n_dec, const int32_t* dec_dims, int32_t out, int32_t bones);
+/* Workgroups of p3d_vae_decode per CU: 1 .. what a CU's LDS holds, 0 the default (as many as it
+ * holds, four at the most; MEASUREMENTS.md §20).  Same bits whatever the grid. */
+int p3d_vae_dec_set_grid(p3d_vae* v, int32_t wgs_per_cu);
+
+/* ELBO.compute_loss (losses.py:14-40): loss3_dev =[likef mean_B like, kcsf mean_B kcs,
  * dklf mean_B dkl] for factors = {likef, kcsf, dklf}; B <= max_batch.  kcsf must be 0 unless
  * out == 48 (P3D_ERR_ARG).
  * Bones filter: factors[4] = {mag, cos, dkl, ang}, t is [B, 64] and loss3_dev receives FOUR floats
