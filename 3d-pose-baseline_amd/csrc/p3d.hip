@@ -2610,874 +2610,7 @@ extern "C" uint32_t p3d_crc32c(const void* data, int64_t n, uint32_t crc) {
   return ~c;
 }
 
-// =====================================================================================
-// The VAE pose filter (include/p3d.h; kernels in p3d_vae.h)
-// =====================================================================================
-struct p3d_vae {
-  VaeDesc desc{};
-  std::vector<std::string> names;       // Keras order; tensor i is desc.T[i]
-  int max_batch = 0, form = 0, cus = 0;
-  int kind = P3D_VAE_KIND_ELBO;         // the loss kind (and, bones, the decoder's mag1 / {mag2, cos2} end)
-  uint64_t seed = 0;
-  size_t lds = 0;                       // dynamic LDS bytes of k_vae_fwd / k_vae_step
-  int64_t ws_floats = 0;
-  VaeDesc* d_desc = nullptr;
-  float* params = nullptr; float* grads = nullptr; float* am = nullptr; float* av = nullptr;
-  float* pk = nullptr; float* ws = nullptr;
-  int* pkidx = nullptr;                 // flat element -> packed copy (device)
-  VaeState* st = nullptr;
-  // the sequence filter (k_vae_seq / k_vae_seq4): 0 seq_lds = this shape has none; form 1 is the
-  // default by measurement (MEASUREMENTS.md §14: 5.5 against 14.6 us per frame step at H3.6M size)
-  int seq_form = 1, seq_len = 0, seq_xoff = 0, seq_toff = 0, seq_ldt = 0, seq_moff = 0;
-  size_t seq_lds = 0;
-  // the wide form (in > 256; kernels in p3d_vae_wide.h): `desc` is then the core -- the filter
-  // behind layer 0, whose input is h0 [B, n0] -- and layer 0 (P0 = (in + 1) n0 floats) leads the
-  // flat buffers; the core's tensors follow at flat + P0.  Narrow: P0 = 0, Ptot = desc.P.
-  int wide = 0, in = 0, n0 = 0, P0 = 0, Ptot = 0;
-  std::vector<VaeTensor> tensors;       // the full parameter table (flat offsets into the master buffers)
-  int64_t h0_off = 0, dz0_off = 0;      // float offsets of h0 and dz0 in the workspace
-  // the decoder on its own (k_vae_dec; kernels in p3d_vae_dec.h): the decoder-only descriptor, the
-  // float offset of its parameters in the packed copy, its dynamic LDS and its workgroups per CU
-  VaeDesc dec{};
-  VaeDesc* d_dec = nullptr;
-  int dec_base = 0, dec_wgs = 0;
-  size_t dec_lds = 0;
-};
-
-namespace {
-
-int ceil16(int n) { return (n + 15) / 16 * 16; }
-
-// The layout of a filter (host only): layers, the packed copy, a wave's LDS area, the master
-// tensors.  wpad = 4 staggers the packed rows over the LDS banks for the data-gradient reads;
-// 0 is the fall-back when that does not fit; stage_x keeps the 16-row input tile in LDS too (else
-// layer 0 reads x from global memory).  kind = bones: behind the dec_dim layers come mag1 (16,
-// ReLU) and one packed output layer [16, 64] = {mag2 | cos2} (models.py:555-566; cos1 is not
-// reachable from the decoder's outputs and is not part of the model).  Returns the dynamic LDS bytes.
-size_t vae_layout(VaeDesc& d, std::vector<std::string>& names, int kind, int in, int n_enc, const int32_t* enc,
-                  int latent, int n_dec, const int32_t* dec, int out, int wpad, int stage_x) {
-  d = VaeDesc{};
-  names.clear();
-  d.in = in; d.latent = latent; d.out = out;
-  int pk = 0, act = 0, flat = 0, prev = in;
-  auto tensor = [&](const std::string& name, int K, int N, int pkoff, int ld) {
-    d.T[d.nt++] = VaeTensor{flat, K, N, pkoff, ld};
-    names.push_back(name);
-    flat += K * N;
-    return flat - K * N;
-  };
-  auto layer = [&](int K, int N, int relu) -> VaeLayer& {
-    VaeLayer& L = d.L[d.nl++];
-    L.K = K; L.N = N; L.Np = ceil16(N); L.ld = L.Np + wpad; L.relu = relu;
-    L.wpk = pk; pk += K * L.ld;
-    L.bpk = pk; pk += L.Np;
-    L.aout = act; L.ldo = L.Np + 2; act += 16 * L.ldo;
-    L.split = N; L.fw2 = L.fb2 = 0;
-    return L;
-  };
-  for (int e = 0; e < n_enc; ++e) {
-    VaeLayer& L = layer(prev, enc[e], 1);
-    const std::string s = "enc_h_" + std::to_string(enc[e]);
-    L.fw = tensor(s + "/kernel", L.K, L.N, L.wpk, L.ld);
-    L.fb = tensor(s + "/bias", 1, L.N, L.bpk, L.Np);
-    prev = enc[e];
-  }
-  {
-    d.head = d.nl;
-    VaeLayer& L = layer(prev, 2 * latent, 0);
-    L.split = latent;
-    L.fw = tensor("mean/kernel", L.K, latent, L.wpk, L.ld);
-    L.fb = tensor("mean/bias", 1, latent, L.bpk, L.Np);
-    L.fw2 = tensor("log_varianze/kernel", L.K, latent, L.wpk + latent, L.ld);
-    L.fb2 = tensor("log_varianze/bias", 1, latent, L.bpk + latent, L.Np);
-    prev = latent;
-  }
-  const bool bones = kind == P3D_VAE_KIND_BONES;
-  for (int e = 0; e <= n_dec; ++e) {   // (behind the dec_dim layers: dec_f_out, or the bones filter's mag1)
-    const int N = e < n_dec ? dec[e] : (bones ? 16 : out);
-    VaeLayer& L = layer(prev, N, e < n_dec || bones);
-    const std::string s = e < n_dec ? "dec_f_" + std::to_string(N) : std::string(bones ? "mag1" : "dec_f_out");
-    L.fw = tensor(s + "/kernel", L.K, L.N, L.wpk, L.ld);
-    L.fb = tensor(s + "/bias", 1, L.N, L.bpk, L.Np);
-    prev = N;
-  }
-  if (bones) {   // mag2 (16) and cos2 (48), both on mag1's output: one packed layer split like the head
-    VaeLayer& L = layer(prev, 64, 0);
-    L.split = 16;
-    L.fw = tensor("mag2/kernel", L.K, 16, L.wpk, L.ld);
-    L.fb = tensor("mag2/bias", 1, 16, L.bpk, L.Np);
-    L.fw2 = tensor("cos2/kernel", L.K, 48, L.wpk + 16, L.ld);
-    L.fb2 = tensor("cos2/bias", 1, 48, L.bpk + 16, L.Np);
-  }
-  d.ldz = ceil16(latent) + 2; d.zbuf = act; act += 16 * d.ldz;
-  d.lde = d.ldz; d.ebuf = act; act += 16 * d.lde;
-  d.ldb = 50; d.bt = act;
-  if (out == 48 || bones) act += 16 * d.ldb;   // (bones: the 48 target cosines of the ANG term)
-  d.ldx = ceil16(in) + 2; d.xbuf = -1;
-  if (stage_x) { d.xbuf = act; act += 16 * d.ldx; }
-  for (int l = 0; l < d.nl; ++l) {
-    VaeLayer& L = d.L[l];
-    if (l == 0) { L.ain = d.xbuf; L.lda = d.xbuf >= 0 ? d.ldx : in; }
-    else if (l == d.head + 1) { L.ain = d.zbuf; L.lda = d.ldz; }
-    else { L.ain = d.L[l - 1].aout; L.lda = d.L[l - 1].ldo; }
-  }
-  d.P = flat;
-  d.Ppk = (pk + 3) / 4 * 4;
-  d.act = (act + 3) / 4 * 4;
-  return sizeof(float) * ((size_t)d.Ppk + 4 * (size_t)d.act + 64 * 4);
-}
-
-// the roomiest layout that fits one workgroup's LDS (else the last one's size, over the limit)
-size_t vae_best_layout(VaeDesc& d, std::vector<std::string>& names, int kind, int in, int n_enc, const int32_t* enc,
-                       int latent, int n_dec, const int32_t* dec, int out) {
-  const int tries[3][2] = {{4, 1}, {4, 0}, {0, 0}};
-  size_t lds = 0;
-  for (auto& t : tries) {
-    lds = vae_layout(d, names, kind, in, n_enc, enc, latent, n_dec, dec, out, t[0], t[1]);
-    if (lds <= P3D_VAE_LDS_LIMIT) break;
-  }
-  return lds;
-}
-
-// The layout of any accepted shape: narrow as vae_best_layout; wide (in > 256) the core's layout
-// with layer 0 leading the names and the parameter table.  Returns the largest workgroup's LDS
-// (the wide kernels of layer 0 use none).
-size_t vae_full_layout(VaeDesc& d, std::vector<std::string>& names, std::vector<VaeTensor>& tensors, int& P0, int kind,
-                       int in, int n_enc, const int32_t* enc, int latent, int n_dec, const int32_t* dec, int out) {
-  tensors.clear();
-  P0 = 0;
-  if (in <= 256) {
-    const size_t lds = vae_best_layout(d, names, kind, in, n_enc, enc, latent, n_dec, dec, out);
-    tensors.assign(d.T, d.T + d.nt);
-    return lds;
-  }
-  std::vector<std::string> core;
-  const size_t lds = vae_best_layout(d, core, kind, enc[0], n_enc - 1, enc + 1, latent, n_dec, dec, out);
-  P0 = (in + 1) * enc[0];
-  const std::string s = "enc_h_" + std::to_string(enc[0]);
-  names = {s + "/kernel", s + "/bias"};
-  names.insert(names.end(), core.begin(), core.end());
-  tensors.push_back(VaeTensor{0, in, enc[0], -1, 0});
-  tensors.push_back(VaeTensor{in * enc[0], 1, enc[0], -1, 0});
-  for (int t = 0; t < d.nt; ++t) {
-    VaeTensor T = d.T[t];
-    T.flat += P0;
-    tensors.push_back(T);
-  }
-  return lds;
-}
-
-// The sequence filter's LDS behind the packed copy (float offsets): ONE tile's activation area, the
-// [16, in] state tile (the area's own input tile where the layout stages one), the frame's target
-// tile and the 16 rows' first frame (int64) and frame count (int).  Returns the dynamic LDS bytes.
-size_t vae_seq_layout(const VaeDesc& d, int& xoff, int& toff, int& ldt, int& moff) {
-  int act = d.act;
-  xoff = d.xbuf;
-  if (xoff < 0) { xoff = act; act += (16 * d.ldx + 3) / 4 * 4; }
-  ldt = ceil16(d.out) + 2;
-  toff = act; act += 16 * ldt;
-  moff = act; act += 16 * 2 + 16;   // (act stays a multiple of 4: the int64 offsets are aligned)
-  return sizeof(float) * ((size_t)d.Ppk + (size_t)act);
-}
-
-// The decoder-only descriptor of a laid-out filter: the packed range of layers head + 1 .. nl - 1
-// (`base` floats into the packed copy; vae_layout packs the layers in order, which is checked here)
-// with wpk / bpk rebased to it, and a wave's area shrunk to the z tile and the decoder's
-// activations.  Returns the dynamic LDS bytes of k_vae_dec, 0 if the range is not contiguous.
-size_t vae_dec_layout(const VaeDesc& full, VaeDesc& dd, int& base) {
-  dd = full;
-  base = full.L[full.head + 1].wpk;
-  int pk = base, act = 0;
-  dd.zbuf = act; act += 16 * dd.ldz;
-  dd.ebuf = dd.bt = dd.xbuf = -1;
-  for (int l = 0; l <= full.head; ++l) dd.L[l] = VaeLayer{};
-  for (int l = full.head + 1; l < full.nl; ++l) {
-    VaeLayer& L = dd.L[l];
-    if (L.wpk != pk || L.bpk != pk + L.K * L.ld) return 0;
-    pk = L.bpk + L.Np;
-    L.wpk -= base; L.bpk -= base;
-    L.ain = l == full.head + 1 ? dd.zbuf : dd.L[l - 1].aout;
-    L.lda = l == full.head + 1 ? dd.ldz : dd.L[l - 1].ldo;
-    L.aout = act; act += 16 * L.ldo;
-  }
-  if ((pk + 3) / 4 * 4 != full.Ppk || base % 4 != 0) return 0;
-  dd.Ppk = full.Ppk - base;
-  dd.act = (act + 3) / 4 * 4;
-  return sizeof(float) * ((size_t)dd.Ppk + 4 * (size_t)dd.act);
-}
-
-// workgroups of k_vae_dec per CU: as many as the CU's LDS holds, four at the most
-int vae_dec_fit(size_t lds) {
-  const int fit = (int)(P3D_VAE_LDS_LIMIT / (lds ? lds : 1));
-  return fit < 1 ? 1 : (fit > 4 ? 4 : fit);
-}
-
-int vae_check_call(const p3d_vae* v, const void* x, int64_t B, const char* what) {
-  if (!v || !x) return fail(P3D_ERR_ARG, std::string(what) + ": null argument");
-  if (B < 1 || B > (1 << 20)) return fail(P3D_ERR_ARG, std::string(what) + ": B must be in 1 .. 2^20");
-  return P3D_OK;
-}
-
-// A caller's p3d_vae_cat checked against (in, B) and turned into the kernels' form.  Pure host code.
-int vae_cat_check(const p3d_vae_cat* c, int32_t in, int64_t B, const char* what, VaeCat* out) {
-  const std::string w(what);
-  if (!c) return fail(P3D_ERR_ARG, w + ": null argument");
-  if (c->n < 1 || c->n > 4) return fail(P3D_ERR_ARG, w + ": 1 to 4 segments");
-  VaeCat k{};
-  k.n = c->n;
-  int sum = 0;
-  for (int s = 0; s < c->n; ++s) {
-    if (c->w[s] < 8 || c->w[s] % 8 != 0) return fail(P3D_ERR_ARG, w + ": segment widths must be multiples of 8");
-    if (!c->p[s]) return fail(P3D_ERR_ARG, w + ": null segment pointer");
-    if ((uintptr_t)c->p[s] % 16 != 0) return fail(P3D_ERR_ARG, w + ": segments must be 16-byte aligned");
-    if (c->rows[s] < 1 || c->rows[s] > (INT64_MAX >> 16))
-      return fail(P3D_ERR_ARG, w + ": a segment's table needs at least one row");
-    if (!c->idx[s] && c->rows[s] < B) return fail(P3D_ERR_ARG, w + ": a segment without an index needs B rows");
-    k.w[s] = c->w[s]; k.off[s] = sum; k.p[s] = c->p[s]; k.idx[s] = c->idx[s]; k.rows[s] = c->rows[s];
-    sum += c->w[s];
-    if (sum > 2048) break;
-  }
-  if (in >= 0 && sum != in)   // (in < 0: no filter to compare with)
-    return fail(P3D_ERR_ARG, w + ": segment widths must sum to in (" + std::to_string(in) + ")");
-  if (out) *out = k;
-  return P3D_OK;
-}
-
-VaeCat vae_cat_plain(const float* x, int in, int64_t B) {
-  VaeCat k{};
-  k.n = 1; k.w[0] = in; k.p[0] = x; k.rows[0] = B;
-  return k;
-}
-
-VaeArgs vae_args(const p3d_vae* v, const float* x, const float* t, int64_t B, const float* eps, uint64_t ctr) {
-  VaeArgs a{};
-  a.desc = v->d_desc; a.pk = v->pk; a.x = x; a.t = t; a.eps = eps; a.B = B;
-  a.seed = v->seed; a.ctr = ctr;
-  a.ctr_dev = ctr == P3D_CTR_GLOBAL_STEP ? v->st : nullptr;
-  a.w = v->params + v->P0; a.m = v->am + v->P0; a.v = v->av + v->P0; a.pk_out = v->pk; a.st = v->st;
-  a.pkidx = v->pkidx;
-  a.nblk = 1;
-  a.nterm = v->kind == P3D_VAE_KIND_BONES ? 4 : 3;
-  return a;
-}
-
-VaeWideArgs vae_wide_args(const p3d_vae* v, const VaeCat& cat, int64_t B) {
-  VaeWideArgs wa{};
-  wa.cat = cat; wa.B = B; wa.in = v->in; wa.n0 = v->n0;
-  wa.w0 = v->params; wa.h0 = v->ws + v->h0_off; wa.dz0 = v->ws + v->dz0_off;
-  wa.g = v->grads; wa.w = v->params; wa.m = v->am; wa.v = v->av; wa.st = v->st;
-  return wa;
-}
-
-// the wide form's first launch: h0 = relu(x W0 + b0)
-int vae_wide_fwd(const p3d_vae* v, const VaeWideArgs& wa, hipStream_t st) {
-  const int64_t units = ((wa.B + 15) / 16) * ((v->n0 + 15) / 16);
-  const int64_t nwg = (units + 3) / 4, cap = (int64_t)v->cus * 8;
-  hipLaunchKernelGGL(k_vae_wide_fwd, dim3((unsigned)(nwg < cap ? nwg : cap)), dim3(256), 0, st, wa);
-  LAUNCH_CHECK("k_vae_wide_fwd");
-  return P3D_OK;
-}
-
-int vae_forward(p3d_vae* v, const float* x, const VaeCat* cat, int64_t B, const float* eps, uint64_t ctr, float* y,
-                float* mean, float* log_var, float* z, const float* target, float* row_terms, void* stream,
-                const char* what) {
-  if ((row_terms != nullptr) != (target != nullptr))
-    return fail(P3D_ERR_ARG, std::string(what) + ": row_terms and target go together");
-  const hipStream_t st = (hipStream_t)stream;
-  if (v->wide) {
-    if (B > v->max_batch) return fail(P3D_ERR_ARG, std::string(what) + ": B exceeds max_batch");
-    const VaeWideArgs wa = vae_wide_args(v, cat ? *cat : vae_cat_plain(x, v->in, B), B);
-    if (int rc = vae_wide_fwd(v, wa, st)) return rc;
-    x = wa.h0;
-    cat = nullptr;
-  }
-  VaeArgs a = vae_args(v, x, target, B, eps, ctr);
-  a.y = y; a.mean = mean; a.log_var = log_var; a.z = z; a.row_terms = row_terms;
-  if (cat) a.cat = *cat;
-  const int64_t nwg = (B + 63) / 64;
-  const int grid = (int)(nwg < v->cus ? nwg : v->cus);
-  const bool bones = v->kind == P3D_VAE_KIND_BONES;
-  if (cat) hipLaunchKernelGGL(bones ? k_vae_bones_fwd_cat : k_vae_fwd_cat, dim3(grid), dim3(256), v->lds, st, a);
-  else hipLaunchKernelGGL(bones ? k_vae_bones_fwd : k_vae_fwd, dim3(grid), dim3(256), v->lds, st, a);
-  LAUNCH_CHECK("k_vae_fwd");
-  return P3D_OK;
-}
-
-// loss (backward = 0), gradient (backward = 1) or training step (adam = 1) over B rows; the input
-// is x or, where `cat` is set, the concatenated segments
-int vae_step(p3d_vae* v, const float* x, const VaeCat* cat, const float* t, int64_t B, const float* eps, uint64_t ctr,
-             const float* factors, int backward, int adam, float lr, float* loss3, void* stream,
-             const char* what) {
-  if (!t || !factors || !loss3) return fail(P3D_ERR_ARG, std::string(what) + ": null argument");
-  if (B > v->max_batch) return fail(P3D_ERR_ARG, std::string(what) + ": B exceeds max_batch");
-  const bool bones = v->kind == P3D_VAE_KIND_BONES;
-  if (!bones && factors[1] != 0.0f && v->desc.out != 48)
-    return fail(P3D_ERR_ARG, std::string(what) + ": the KCS term needs out == 48 (kcs_factor must be 0)");
-  const hipStream_t st = (hipStream_t)stream;
-  VaeWideArgs wa{};
-  if (v->wide) {
-    wa = vae_wide_args(v, cat ? *cat : vae_cat_plain(x, v->in, B), B);
-    wa.adam = adam;
-    if (int rc = vae_wide_fwd(v, wa, st)) return rc;
-    x = wa.h0;
-    cat = nullptr;
-  }
-  VaeArgs a = vae_args(v, x, t, B, eps, ctr);
-  if (cat) a.cat = *cat;
-  const int nblk = (int)((B + 63) / 64);
-  const bool one = nblk == 1 && v->form == 0;
-  a.backward = backward; a.adam = adam; a.lr = lr;
-  a.nblk = nblk;
-  if (bones) {   // factors = {mag, cos, dkl, ang} (losses.py:143-152)
-    a.c_like = (float)(2.0 * (double)factors[0] / (16.0 * (double)B));
-    a.c_cos = (float)((double)factors[1] / (8.0 * (double)B));
-    a.c_kcs = (float)((double)factors[3] / (256.0 * (double)B));
-  } else {
-    a.c_like = (float)(2.0 * (double)factors[0] / ((double)B * v->desc.out));
-    a.c_kcs = (float)((double)factors[1] / (double)B);
-  }
-  a.c_kl = (float)((double)factors[2] / (double)B);
-  for (int j = 0; j < a.nterm; ++j) a.f[j] = factors[j];
-  a.lpart = v->ws + (int64_t)nblk * v->desc.P;
-  a.loss3 = loss3;
-  a.gout = one ? v->grads + v->P0 : v->ws;
-  a.tail = one;
-  a.dx = v->wide ? v->ws + v->dz0_off : nullptr;
-  const int grid = nblk < v->cus ? nblk : v->cus;
-  if (v->wide) hipLaunchKernelGGL(bones ? k_vae_bones_step_dx : k_vae_step_dx, dim3(grid), dim3(256), v->lds, st, a);
-  else if (cat) hipLaunchKernelGGL(bones ? k_vae_bones_step_cat : k_vae_step_cat, dim3(grid), dim3(256), v->lds, st, a);
-  else hipLaunchKernelGGL(bones ? k_vae_bones_step : k_vae_step, dim3(grid), dim3(256), v->lds, st, a);
-  LAUNCH_CHECK("k_vae_step");
-  if (!one) {
-    // the partials form: block sums (gradient and loss) and the optimizer, behind it on the stream
-    hipLaunchKernelGGL(k_vae_reduce_adam, dim3(backward ? (v->desc.P + 255) / 256 : 1), dim3(256), 0, st, a,
-                       v->grads + v->P0);
-    LAUNCH_CHECK("k_vae_reduce_adam");
-  }
-  if (v->wide && backward) {   // layer 0's gradient (and optimizer), behind dz0 and alpha on the stream
-    const int units = ((v->in + 15) / 16 + 1) * ((v->n0 + 15) / 16);
-    hipLaunchKernelGGL(k_vae_wide_wgrad_adam, dim3((units + 3) / 4), dim3(256), 0, st, wa);
-    LAUNCH_CHECK("k_vae_wide_wgrad_adam");
-  }
-  return P3D_OK;
-}
-
-}  // namespace
-
-namespace {
-int vae_check_shape(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent, int32_t n_dec,
-                    const int32_t* dec_dims, int32_t out) {
-  if (!enc_dims || !dec_dims) return fail(P3D_ERR_ARG, "p3d_vae_create: null argument");
-  auto width = [](int w, int hi) { return w >= 8 && w <= hi && w % 8 == 0; };
-  if (!width(in, 2048)) return fail(P3D_ERR_ARG, "p3d_vae_create: in must be a multiple of 8 in 8 .. 2048");
-  if (n_enc < 1 || n_enc > 4 || n_dec < 1 || n_dec > 4)
-    return fail(P3D_ERR_ARG, "p3d_vae_create: 1 to 4 hidden layers on each side");
-  for (int e = 0; e < n_enc; ++e)
-    if (!width(enc_dims[e], 256)) return fail(P3D_ERR_ARG, "p3d_vae_create: hidden widths must be multiples of 8 in 8 .. 256");
-  for (int e = 0; e < n_dec; ++e)
-    if (!width(dec_dims[e], 256)) return fail(P3D_ERR_ARG, "p3d_vae_create: hidden widths must be multiples of 8 in 8 .. 256");
-  if (!width(latent, 64)) return fail(P3D_ERR_ARG, "p3d_vae_create: latent must be a multiple of 8 in 8 .. 64");
-  if (!width(out, 64)) return fail(P3D_ERR_ARG, "p3d_vae_create: out must be a multiple of 8 in 8 .. 64");
-  return P3D_OK;
-}
-}  // namespace
-
-extern "C" int64_t p3d_vae_lds_bytes(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent, int32_t n_dec,
-                                     const int32_t* dec_dims, int32_t out) {
-  if (vae_check_shape(in, n_enc, enc_dims, latent, n_dec, dec_dims, out)) return 0;
-  VaeDesc d;
-  std::vector<std::string> names;
-  std::vector<VaeTensor> tensors;
-  int P0;
-  return (int64_t)vae_full_layout(d, names, tensors, P0, P3D_VAE_KIND_ELBO, in, n_enc, enc_dims, latent, n_dec, dec_dims,
-                                  out);
-}
-
-extern "C" int64_t p3d_vae_dec_lds_bytes(int32_t latent, int32_t n_dec, const int32_t* dec_dims, int32_t out,
-                                         int32_t bones) {
-  const int32_t enc[1] = {8};   // (the decoder's layout does not depend on the encoder)
-  if (bones != 0 && bones != 1) return 0;
-  if (vae_check_shape(8, 1, enc, latent, n_dec, dec_dims, bones ? 64 : out)) return 0;
-  VaeDesc d, dd;
-  std::vector<std::string> names;
-  int base;
-  vae_layout(d, names, bones ? P3D_VAE_KIND_BONES : P3D_VAE_KIND_ELBO, 8, 1, enc, latent, n_dec, dec_dims,
-             bones ? 64 : out, 4, 1);
-  const size_t lds = vae_dec_layout(d, dd, base);
-  return lds <= P3D_VAE_LDS_LIMIT ? (int64_t)lds : 0;
-}
-
-extern "C" int64_t p3d_vae_bones_lds_bytes(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent,
-                                           int32_t n_dec, const int32_t* dec_dims) {
-  if (vae_check_shape(in, n_enc, enc_dims, latent, n_dec, dec_dims, 64)) return 0;
-  VaeDesc d;
-  std::vector<std::string> names;
-  std::vector<VaeTensor> tensors;
-  int P0;
-  return (int64_t)vae_full_layout(d, names, tensors, P0, P3D_VAE_KIND_BONES, in, n_enc, enc_dims, latent, n_dec, dec_dims,
-                                  64);
-}
-
-namespace {
-int vae_create(int kind, int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent, int32_t n_dec,
-               const int32_t* dec_dims, int32_t out, int32_t max_batch, uint64_t seed, p3d_vae** vout) {
-  if (!vout) return fail(P3D_ERR_ARG, "p3d_vae_create: null argument");
-  if (int rc = vae_check_shape(in, n_enc, enc_dims, latent, n_dec, dec_dims, out)) return rc;
-  if (max_batch < 1 || max_batch > (1 << 20)) return fail(P3D_ERR_ARG, "p3d_vae_create: max_batch must be in 1 .. 2^20");
-  p3d_vae* v = new p3d_vae();
-  v->kind = kind;
-  v->lds = vae_full_layout(v->desc, v->names, v->tensors, v->P0, kind, in, n_enc, enc_dims, latent, n_dec, dec_dims, out);
-  v->wide = in > 256;
-  v->in = in; v->n0 = enc_dims[0];
-  v->Ptot = v->P0 + v->desc.P;
-  if (v->lds > P3D_VAE_LDS_LIMIT) {
-    const size_t need = v->lds;
-    delete v;
-    return fail(P3D_ERR_ARG, "p3d_vae_create: parameters and working space need " + std::to_string(need) +
-                                 " bytes of LDS, a workgroup has " + std::to_string(P3D_VAE_LDS_LIMIT));
-  }
-  v->dec_lds = vae_dec_layout(v->desc, v->dec, v->dec_base);   // (host only: the decoder's range of the packed copy)
-  if (!v->dec_lds || v->dec_lds > v->lds) {
-    delete v;
-    return fail(P3D_ERR_STATE, "p3d_vae_create: the decoder's parameters are not one range of the packed copy");
-  }
-  v->dec_wgs = vae_dec_fit(v->dec_lds);
-  for (size_t i = 0; i < v->names.size(); ++i)
-    for (size_t j = 0; j < i; ++j)
-      if (v->names[i] == v->names[j]) {   // keras: "All layers added to a Model must have unique names"
-        const std::string dup = v->names[i];
-        delete v;
-        return fail(P3D_ERR_ARG, "p3d_vae_create: two layers of one side share the width in " + dup +
-                                     " (keras layer names must be unique)");
-      }
-  v->max_batch = max_batch;
-  v->seed = seed;
-  const int64_t nblk = (max_batch + 63) / 64;
-  v->ws_floats = nblk * ((int64_t)v->desc.P + 4) + 4;
-  if (v->wide) {   // h0 and dz0 behind the core's block partials (offsets fixed by max_batch, multiples of 4)
-    v->h0_off = v->ws_floats;
-    v->dz0_off = v->h0_off + (int64_t)max_batch * v->n0;
-    v->ws_floats = v->dz0_off + (int64_t)max_batch * v->n0;
-  }
-  auto bail = [&](hipError_t e, const char* what) {
-    p3d_vae_destroy(v);
-    return fail(P3D_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-  };
-  hipError_t e;
-  int dev = 0;
-  if ((e = hipGetDevice(&dev)) != hipSuccess) return bail(e, "hipGetDevice");
-  hipDeviceProp_t prop;
-  if ((e = hipGetDeviceProperties(&prop, dev)) != hipSuccess) return bail(e, "hipGetDeviceProperties");
-  v->cus = prop.multiProcessorCount;
-  const size_t pb = sizeof(float) * (size_t)v->Ptot;
-  float** bufs[4] = {&v->params, &v->grads, &v->am, &v->av};
-  for (auto b : bufs) {
-    if ((e = hipMalloc((void**)b, pb)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMemset(*b, 0, pb)) != hipSuccess) return bail(e, "hipMemset");
-  }
-  if ((e = hipMalloc((void**)&v->pk, sizeof(float) * v->desc.Ppk)) != hipSuccess) return bail(e, "hipMalloc");
-  if ((e = hipMemset(v->pk, 0, sizeof(float) * v->desc.Ppk)) != hipSuccess) return bail(e, "hipMemset");
-  if ((e = hipMalloc((void**)&v->ws, sizeof(float) * v->ws_floats)) != hipSuccess) return bail(e, "hipMalloc");
-  if ((e = hipMemset(v->ws, 0, sizeof(float) * v->ws_floats)) != hipSuccess) return bail(e, "hipMemset");
-  if ((e = hipMalloc((void**)&v->d_desc, sizeof(VaeDesc))) != hipSuccess) return bail(e, "hipMalloc");
-  if ((e = hipMemcpy(v->d_desc, &v->desc, sizeof(VaeDesc), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
-  {
-    std::vector<int> idx((size_t)v->desc.P);
-    for (int t = 0; t < v->desc.nt; ++t) {
-      const VaeTensor& T = v->desc.T[t];
-      for (int k = 0; k < T.K; ++k)
-        for (int n = 0; n < T.N; ++n) idx[(size_t)T.flat + (size_t)k * T.N + n] = T.pk + k * T.ld + n;
-    }
-    if ((e = hipMalloc((void**)&v->pkidx, sizeof(int) * idx.size())) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMemcpy(v->pkidx, idx.data(), sizeof(int) * idx.size(), hipMemcpyHostToDevice)) != hipSuccess)
-      return bail(e, "hipMemcpy");
-  }
-  if ((e = hipMalloc((void**)&v->d_dec, sizeof(VaeDesc))) != hipSuccess) return bail(e, "hipMalloc");
-  if ((e = hipMemcpy(v->d_dec, &v->dec, sizeof(VaeDesc), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
-  for (const void* k : {(const void*)k_vae_dec, (const void*)k_vae_bones_dec})
-    if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->dec_lds)) != hipSuccess)
-      return bail(e, "hipFuncSetAttribute(k_vae_dec)");
-  if ((e = hipMalloc((void**)&v->st, sizeof(VaeState))) != hipSuccess) return bail(e, "hipMalloc");
-  const VaeState s0{0, 0.9f, 0.999f, 0.0f, {0, 0, 0}};
-  if ((e = hipMemcpy(v->st, &s0, sizeof(VaeState), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
-  if ((e = hipFuncSetAttribute((const void*)k_vae_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->lds)) != hipSuccess)
-    return bail(e, "hipFuncSetAttribute(k_vae_fwd)");
-  if ((e = hipFuncSetAttribute((const void*)k_vae_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->lds)) != hipSuccess)
-    return bail(e, "hipFuncSetAttribute(k_vae_step)");
-  for (const void* k : {(const void*)k_vae_fwd_cat, (const void*)k_vae_step_cat, (const void*)k_vae_step_dx})
-    if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->lds)) != hipSuccess)
-      return bail(e, "hipFuncSetAttribute(k_vae_*_cat)");
-  if (kind == P3D_VAE_KIND_BONES)
-    for (const void* k : {(const void*)k_vae_bones_fwd, (const void*)k_vae_bones_fwd_cat, (const void*)k_vae_bones_step,
-                          (const void*)k_vae_bones_step_cat, (const void*)k_vae_bones_step_dx})
-      if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->lds)) != hipSuccess)
-        return bail(e, "hipFuncSetAttribute(k_vae_bones_*)");
-  if (kind == P3D_VAE_KIND_ELBO && !v->wide && in % out == 0 && in / out <= P3D_VAE_SEQ_MAX_LEN) {
-    const size_t sl = vae_seq_layout(v->desc, v->seq_xoff, v->seq_toff, v->seq_ldt, v->seq_moff);
-    if (sl <= P3D_VAE_LDS_LIMIT) {
-      v->seq_len = in / out;
-      v->seq_lds = sl;
-      if ((e = hipFuncSetAttribute((const void*)k_vae_seq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sl)) != hipSuccess)
-        return bail(e, "hipFuncSetAttribute(k_vae_seq)");
-      if ((e = hipFuncSetAttribute((const void*)k_vae_seq4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sl)) != hipSuccess)
-        return bail(e, "hipFuncSetAttribute(k_vae_seq4)");
-    }
-  }
-  *vout = v;
-  return P3D_OK;
-}
-}  // namespace
-
-extern "C" int p3d_vae_create(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent, int32_t n_dec,
-                              const int32_t* dec_dims, int32_t out, int32_t max_batch, uint64_t seed, p3d_vae** vout) {
-  return vae_create(P3D_VAE_KIND_ELBO, in, n_enc, enc_dims, latent, n_dec, dec_dims, out, max_batch, seed, vout);
-}
-
-extern "C" int p3d_vae_create_bones(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent, int32_t n_dec,
-                                    const int32_t* dec_dims, int32_t max_batch, uint64_t seed, p3d_vae** vout) {
-  return vae_create(P3D_VAE_KIND_BONES, in, n_enc, enc_dims, latent, n_dec, dec_dims, 64, max_batch, seed, vout);
-}
-
-extern "C" int32_t p3d_vae_kind(const p3d_vae* v) { return v ? v->kind : -1; }
-
-extern "C" int p3d_bones_from_joints(const float* joints, int64_t B, int32_t precise, float* out64, void* stream) {
-  if (!joints || !out64) return fail(P3D_ERR_ARG, "p3d_bones_from_joints: null argument");
-  if (B < 1 || B > (1 << 20)) return fail(P3D_ERR_ARG, "p3d_bones_from_joints: B must be in 1 .. 2^20");
-  if (precise != 0 && precise != 1) return fail(P3D_ERR_ARG, "p3d_bones_from_joints: precise must be 0 or 1");
-  const unsigned grid = (unsigned)((B * 16 + 255) / 256);
-  if (precise) hipLaunchKernelGGL(k_bones_from_joints<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, joints, B, out64);
-  else hipLaunchKernelGGL(k_bones_from_joints<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, joints, B, out64);
-  LAUNCH_CHECK("k_bones_from_joints");
-  return P3D_OK;
-}
-
-extern "C" int p3d_bones_to_joints(const float* bones64, int64_t B, double* joints_f64, void* stream) {
-  if (!bones64 || !joints_f64) return fail(P3D_ERR_ARG, "p3d_bones_to_joints: null argument");
-  if (B < 1 || B > (1 << 20)) return fail(P3D_ERR_ARG, "p3d_bones_to_joints: B must be in 1 .. 2^20");
-  hipLaunchKernelGGL(k_bones_to_joints, dim3((unsigned)((B * 16 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, bones64,
-                     B, joints_f64);
-  LAUNCH_CHECK("k_bones_to_joints");
-  return P3D_OK;
-}
-
-extern "C" int p3d_vae_destroy(p3d_vae* v) {
-  if (!v) return P3D_OK;
-  void* bufs[] = {v->params, v->grads, v->am, v->av, v->pk, v->ws, v->d_desc, v->st, v->pkidx, v->d_dec};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  delete v;
-  return P3D_OK;
-}
-
-extern "C" int p3d_vae_param_count(const p3d_vae* v, int32_t* count) {
-  if (!v || !count) return fail(P3D_ERR_ARG, "p3d_vae_param_count: null argument");
-  *count = (int32_t)v->tensors.size();
-  return P3D_OK;
-}
-
-extern "C" int p3d_vae_param_info(const p3d_vae* v, int32_t idx, const char** name, int64_t* numel, int32_t* rows,
-                                  int32_t* cols, int64_t* offset) {
-  if (!v) return fail(P3D_ERR_ARG, "p3d_vae_param_info: null argument");
-  if (idx < 0 || idx >= (int)v->tensors.size()) return fail(P3D_ERR_ARG, "p3d_vae_param_info: index out of range");
-  const VaeTensor& T = v->tensors[idx];
-  if (name) *name = v->names[idx].c_str();
-  if (numel) *numel = (int64_t)T.K * T.N;
-  if (rows) *rows = T.K;
-  if (cols) *cols = T.N;
-  if (offset) *offset = T.flat;
-  return P3D_OK;
-}
-
-extern "C" int p3d_vae_param_ptr(p3d_vae* v, const char* name, void** dptr, int64_t* numel) {
-  if (!v || !name || !dptr) return fail(P3D_ERR_ARG, "p3d_vae_param_ptr: null argument");
-  for (size_t i = 0; i < v->tensors.size(); ++i)
-    if (v->names[i] == name) {
-      *dptr = v->params + v->tensors[i].flat;
-      if (numel) *numel = (int64_t)v->tensors[i].K * v->tensors[i].N;
-      return P3D_OK;
-    }
-  return fail(P3D_ERR_NOTFOUND, std::string("p3d_vae_param_ptr: no parameter named ") + name);
-}
-
-extern "C" int p3d_vae_flat_ptr(p3d_vae* v, int32_t which, void** dptr, int64_t* numel) {
-  if (!v || !dptr) return fail(P3D_ERR_ARG, "p3d_vae_flat_ptr: null argument");
-  float* const bufs[6] = {v->params, v->grads, v->am, v->av, v->ws, v->pk};
-  if (which < 0 || which > 5) return fail(P3D_ERR_ARG, "p3d_vae_flat_ptr: which must be 0 .. 5");
-  *dptr = bufs[which];
-  if (numel) *numel = which == 4 ? v->ws_floats : which == 5 ? v->desc.Ppk : v->Ptot;
-  return P3D_OK;
-}
-
-extern "C" int p3d_vae_params_updated(p3d_vae* v, void* stream) {
-  if (!v) return fail(P3D_ERR_ARG, "p3d_vae_params_updated: null argument");
-  hipLaunchKernelGGL(k_vae_pack, dim3((v->desc.P + 255) / 256), dim3(256), 0, (hipStream_t)stream, v->desc.P,
-                     (const int*)v->pkidx, (const float*)(v->params + v->P0), v->pk);
-  LAUNCH_CHECK("k_vae_pack");
-  return P3D_OK;
-}
-
-extern "C" int p3d_vae_cat_check(const p3d_vae_cat* cat, int32_t in, int64_t B) {
-  if (B < 1 || B > (1 << 20)) return fail(P3D_ERR_ARG, "p3d_vae_cat_check: B must be in 1 .. 2^20");
-  return vae_cat_check(cat, in, B, "p3d_vae_cat_check", nullptr);
-}
-
-extern "C" int p3d_vae_forward(p3d_vae* v, const float* x, int64_t B, const float* eps, uint64_t ctr, float* y,
-                               float* mean, float* log_var, float* z, const float* target, float* row_terms,
-                               void* stream) {
-  if (int rc = vae_check_call(v, x, B, "p3d_vae_forward")) return rc;
-  return vae_forward(v, x, nullptr, B, eps, ctr, y, mean, log_var, z, target, row_terms, stream, "p3d_vae_forward");
-}
-
-// The errors that need no filter answer first (and without a GPU).
-extern "C" int p3d_vae_decode(p3d_vae* v, const float* z, int64_t B, uint64_t ctr, int64_t row0, float* y,
-                              float* z_out, void* stream) {
-  if (!y) return fail(P3D_ERR_ARG, "p3d_vae_decode: y is null");
-  if (B < 1 || B > (1 << 20)) return fail(P3D_ERR_ARG, "p3d_vae_decode: B must be in 1 .. 2^20");
-  if (z && z_out) return fail(P3D_ERR_ARG, "p3d_vae_decode: z_out receives the drawn z: give z or z_out, not both");
-  if (row0 < 0) return fail(P3D_ERR_ARG, "p3d_vae_decode: row0 must be >= 0");
-  if (ctr == P3D_CTR_GLOBAL_STEP)
-    return fail(P3D_ERR_ARG, "p3d_vae_decode: the prior stream has no device counter (ctr may not be P3D_CTR_GLOBAL_STEP)");
-  if (!v) return fail(P3D_ERR_ARG, "p3d_vae_decode: null handle");
-  VaeDecArgs a{};
-  a.desc = v->d_dec; a.pk = v->pk + v->dec_base; a.z = z; a.B = B; a.row0 = row0;
-  a.seed = v->seed; a.ctr = ctr; a.y = y; a.z_out = z_out;
-  const int64_t nwg = (B + 63) / 64, cap = (int64_t)v->cus * v->dec_wgs;
-  const int grid = (int)(nwg < cap ? nwg : cap);
-  hipLaunchKernelGGL(v->kind == P3D_VAE_KIND_BONES ? k_vae_bones_dec : k_vae_dec, dim3(grid), dim3(256), v->dec_lds,
-                     (hipStream_t)stream, a);
-  LAUNCH_CHECK("k_vae_dec");
-  return P3D_OK;
-}
-
-extern "C" int p3d_vae_dec_set_grid(p3d_vae* v, int32_t wgs_per_cu) {
-  if (!v) return fail(P3D_ERR_ARG, "p3d_vae_dec_set_grid: null handle");
-  const int fit = (int)(P3D_VAE_LDS_LIMIT / v->dec_lds);
-  if (wgs_per_cu < 0 || wgs_per_cu > (fit < 16 ? fit : 16))
-    return fail(P3D_ERR_ARG, "p3d_vae_dec_set_grid: workgroups per CU must be 0 (the default) or 1 .. " +
-                                 std::to_string(fit < 16 ? fit : 16) + " (what a CU's LDS holds)");
-  v->dec_wgs = wgs_per_cu ? wgs_per_cu : vae_dec_fit(v->dec_lds);
-  return P3D_OK;
-}
-
-extern "C" int p3d_vae_loss(p3d_vae* v, const float* x, const float* t, int64_t B, const float* eps, uint64_t ctr,
-                            const float* factors, float* loss3_dev, void* stream) {
-  if (int rc = vae_check_call(v, x, B, "p3d_vae_loss")) return rc;
-  return vae_step(v, x, nullptr, t, B, eps, ctr, factors, 0, 0, 0.0f, loss3_dev, stream, "p3d_vae_loss");
-}
-
-extern "C" int p3d_vae_grad(p3d_vae* v, const float* x, const float* t, int64_t B, const float* eps, uint64_t ctr,
-                            const float* factors, float* loss3_dev, void* stream) {
-  if (int rc = vae_check_call(v, x, B, "p3d_vae_grad")) return rc;
-  return vae_step(v, x, nullptr, t, B, eps, ctr, factors, 1, 0, 0.0f, loss3_dev, stream, "p3d_vae_grad");
-}
-
-extern "C" int p3d_vae_train_step(p3d_vae* v, const float* x, const float* t, int64_t B, const float* eps,
-                                  const float* factors, float lr, float* loss3_dev, void* stream) {
-  if (!(lr >= 0.0f)) return fail(P3D_ERR_ARG, "p3d_vae_train_step: lr must be >= 0");
-  if (int rc = vae_check_call(v, x, B, "p3d_vae_train_step")) return rc;
-  return vae_step(v, x, nullptr, t, B, eps, P3D_CTR_GLOBAL_STEP, factors, 1, 1, lr, loss3_dev, stream,
-                  "p3d_vae_train_step");
-}
-
-// The _cat twins.  The struct's own errors answer first: they need no filter (and no GPU).
-namespace {
-int vae_cat_call(const p3d_vae* v, const p3d_vae_cat* cat, int64_t B, const char* what, VaeCat* k) {
-  if (!cat) return fail(P3D_ERR_ARG, std::string(what) + ": null argument");
-  if (B < 1 || B > (1 << 20)) return fail(P3D_ERR_ARG, std::string(what) + ": B must be in 1 .. 2^20");
-  if (int rc = vae_cat_check(cat, v ? v->in : -1, B, what, k)) return rc;
-  return vae_check_call(v, cat, B, what);
-}
-}  // namespace
-
-extern "C" int p3d_vae_forward_cat(p3d_vae* v, const p3d_vae_cat* cat, int64_t B, const float* eps, uint64_t ctr,
-                                   float* y, float* mean, float* log_var, float* z, const float* target,
-                                   float* row_terms, void* stream) {
-  VaeCat k;
-  if (int rc = vae_cat_call(v, cat, B, "p3d_vae_forward_cat", &k)) return rc;
-  return vae_forward(v, nullptr, &k, B, eps, ctr, y, mean, log_var, z, target, row_terms, stream, "p3d_vae_forward_cat");
-}
-
-extern "C" int p3d_vae_loss_cat(p3d_vae* v, const p3d_vae_cat* cat, const float* t, int64_t B, const float* eps,
-                                uint64_t ctr, const float* factors, float* loss3_dev, void* stream) {
-  VaeCat k;
-  if (int rc = vae_cat_call(v, cat, B, "p3d_vae_loss_cat", &k)) return rc;
-  return vae_step(v, nullptr, &k, t, B, eps, ctr, factors, 0, 0, 0.0f, loss3_dev, stream, "p3d_vae_loss_cat");
-}
-
-extern "C" int p3d_vae_grad_cat(p3d_vae* v, const p3d_vae_cat* cat, const float* t, int64_t B, const float* eps,
-                                uint64_t ctr, const float* factors, float* loss3_dev, void* stream) {
-  VaeCat k;
-  if (int rc = vae_cat_call(v, cat, B, "p3d_vae_grad_cat", &k)) return rc;
-  return vae_step(v, nullptr, &k, t, B, eps, ctr, factors, 1, 0, 0.0f, loss3_dev, stream, "p3d_vae_grad_cat");
-}
-
-extern "C" int p3d_vae_train_step_cat(p3d_vae* v, const p3d_vae_cat* cat, const float* t, int64_t B, const float* eps,
-                                      const float* factors, float lr, float* loss3_dev, void* stream) {
-  if (!(lr >= 0.0f)) return fail(P3D_ERR_ARG, "p3d_vae_train_step_cat: lr must be >= 0");
-  VaeCat k;
-  if (int rc = vae_cat_call(v, cat, B, "p3d_vae_train_step_cat", &k)) return rc;
-  return vae_step(v, nullptr, &k, t, B, eps, P3D_CTR_GLOBAL_STEP, factors, 1, 1, lr, loss3_dev, stream,
-                  "p3d_vae_train_step_cat");
-}
-
-extern "C" int p3d_vae_adam_apply(p3d_vae* v, float lr, void* stream) {
-  if (!v || !(lr >= 0.0f)) return fail(P3D_ERR_ARG, "p3d_vae_adam_apply: bad argument");
-  VaeArgs a = vae_args(v, nullptr, nullptr, 1, nullptr, 0);
-  a.backward = 1; a.adam = 1; a.nblk = 1; a.gout = v->grads + v->P0; a.loss3 = nullptr;
-  hipLaunchKernelGGL(k_vae_alpha, dim3(1), dim3(1), 0, (hipStream_t)stream, v->st, lr);
-  LAUNCH_CHECK("k_vae_alpha");
-  hipLaunchKernelGGL(k_vae_reduce_adam, dim3((v->desc.P + 255) / 256), dim3(256), 0, (hipStream_t)stream, a,
-                     v->grads + v->P0);
-  LAUNCH_CHECK("k_vae_reduce_adam");
-  if (v->wide) {
-    hipLaunchKernelGGL(k_vae_wide_adam, dim3((v->P0 + 255) / 256), dim3(256), 0, (hipStream_t)stream, v->P0,
-                       (const float*)v->grads, v->params, v->am, v->av, (const VaeState*)v->st);
-    LAUNCH_CHECK("k_vae_wide_adam");
-  }
-  return P3D_OK;
-}
-
-extern "C" int p3d_vae_set_form(p3d_vae* v, int32_t form) {
-  if (!v || (form != 0 && form != 1)) return fail(P3D_ERR_ARG, "p3d_vae_set_form: form must be 0 or 1");
-  v->form = form;
-  return P3D_OK;
-}
-
-extern "C" int p3d_vae_get_step(const p3d_vae* v, int64_t* step, float* beta1_power, float* beta2_power) {
-  if (!v) return fail(P3D_ERR_ARG, "p3d_vae_get_step: null argument");
-  VaeState s;
-  HIP_TRY(hipMemcpy(&s, v->st, sizeof(s), hipMemcpyDeviceToHost));
-  if (step) *step = s.step;
-  if (beta1_power) *beta1_power = s.b1p;
-  if (beta2_power) *beta2_power = s.b2p;
-  return P3D_OK;
-}
-
-extern "C" int p3d_vae_set_step(p3d_vae* v, int64_t step, float beta1_power, float beta2_power) {
-  if (!v || step < 0) return fail(P3D_ERR_ARG, "p3d_vae_set_step: bad argument");
-  const VaeState s{step, beta1_power, beta2_power, 0.0f, {0, 0, 0}};
-  HIP_TRY(hipMemcpy(v->st, &s, sizeof(s), hipMemcpyHostToDevice));
-  return P3D_OK;
-}
-
-extern "C" int p3d_vae_eps(uint64_t seed, uint64_t ctr, int64_t row0, int64_t B, int32_t latent, float* out,
-                           void* stream) {
-  if (!out) return fail(P3D_ERR_ARG, "p3d_vae_eps: null argument");
-  if (B < 1 || B > (1 << 20) || row0 < 0) return fail(P3D_ERR_ARG, "p3d_vae_eps: B must be in 1 .. 2^20, row0 >= 0");
-  if (latent < 4 || latent > 64 || latent % 4 != 0) return fail(P3D_ERR_ARG, "p3d_vae_eps: latent must be a multiple of 4 in 4 .. 64");
-  const int64_t units = B * (latent / 4);
-  hipLaunchKernelGGL(k_vae_eps, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seed, ctr,
-                     row0, B, (int)latent, out);
-  LAUNCH_CHECK("k_vae_eps");
-  return P3D_OK;
-}
-
-namespace {
-int vae_add_noise(const float* src, int64_t rows, int32_t d, const int64_t* starts, int32_t width, int64_t B,
-                  uint64_t seed, uint64_t ctr, int64_t row0, float noise, float offset, float joint_scale,
-                  uint64_t thr, float* out, void* stream, const char* what) {
-  const std::string w(what);
-  if (!src || !out) return fail(P3D_ERR_ARG, w + ": null argument");
-  if (width < 12 || width > P3D_NOISE_MAX_WIDTH || width % 12 != 0)
-    return fail(P3D_ERR_ARG, w + ": width must be a multiple of 12 in 12 .. 240");
-  if (d < 4 || d % 4 != 0) return fail(P3D_ERR_ARG, w + ": d must be a positive multiple of 4");
-  if (width % d != 0) return fail(P3D_ERR_ARG, w + ": width must be a multiple of d");
-  if (B < 1 || B > (1 << 20)) return fail(P3D_ERR_ARG, w + ": B must be in 1 .. 2^20");
-  if (!aligned16(src) || !aligned16(out)) return fail(P3D_ERR_ARG, w + ": src and out must be 16-byte aligned");
-  if (((uintptr_t)starts & 7) != 0) return fail(P3D_ERR_ARG, w + ": starts must be 8-byte aligned");
-  const uintptr_t s0 = (uintptr_t)src, o0 = (uintptr_t)out;
-  const bool overlap = rows > 0 && s0 < o0 + (uintptr_t)B * width * 4 && o0 < s0 + (uintptr_t)rows * d * 4;
-  if (starts) {
-    if (rows < width / d) return fail(P3D_ERR_ARG, w + ": the table has fewer rows than a window");
-    if (overlap) return fail(P3D_ERR_ARG, w + ": in the window form out may not overlap src");
-  } else {
-    if (width != d) return fail(P3D_ERR_ARG, w + ": without starts width must equal d");
-    if (rows < B) return fail(P3D_ERR_ARG, w + ": without starts the table needs at least B rows");
-    if (overlap && src != out) return fail(P3D_ERR_ARG, w + ": out may be src itself, not another overlapping range");
-  }
-  NoiseArgs a;
-  a.src = src; a.rows = rows; a.starts = starts; a.B = B; a.row0 = row0; a.seed = seed; a.ctr = ctr; a.thr = thr;
-  a.noise = noise; a.offset = offset; a.joint_scale = joint_scale; a.d = d; a.width = width;
-  const uint64_t c4n = (uint64_t)(width / 4);
-  a.magic = (uint32_t)(((1ull << 32) + c4n - 1) / c4n);
-  a.out = out;
-  hipLaunchKernelGGL(k_vae_noise, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  LAUNCH_CHECK("k_vae_noise");
-  return P3D_OK;
-}
-}  // namespace
-
-extern "C" int p3d_vae_add_noise(const float* src, int64_t rows, int32_t d, const int64_t* starts, int32_t width,
-                                 int64_t B, uint64_t seed, uint64_t ctr, int64_t row0, float noise, float offset,
-                                 float joint_scale, float* out, void* stream) {
-  return vae_add_noise(src, rows, d, starts, width, B, seed, ctr, row0, noise, offset, joint_scale,
-                       P3D_NOISE_THRESHOLD, out, stream, "p3d_vae_add_noise");
-}
-
-extern "C" int p3d_vae_add_noise_thr(const float* src, int64_t rows, int32_t d, const int64_t* starts, int32_t width,
-                                     int64_t B, uint64_t seed, uint64_t ctr, int64_t row0, float noise, float offset,
-                                     float joint_scale, uint64_t threshold, float* out, void* stream) {
-  if (threshold > (1ull << 32)) return fail(P3D_ERR_ARG, "p3d_vae_add_noise_thr: threshold must be in 0 .. 2^32");
-  return vae_add_noise(src, rows, d, starts, width, B, seed, ctr, row0, noise, offset, joint_scale, threshold, out,
-                       stream, "p3d_vae_add_noise_thr");
-}
-
-extern "C" int64_t p3d_vae_seq_lds_bytes(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent,
-                                         int32_t n_dec, const int32_t* dec_dims, int32_t out, int32_t form) {
-  if (form != 0 && form != 1) return 0;
-  if (vae_check_shape(in, n_enc, enc_dims, latent, n_dec, dec_dims, out)) return 0;
-  if (in > 256 || in % out != 0 || in / out > P3D_VAE_SEQ_MAX_LEN) return 0;
-  VaeDesc d;
-  std::vector<std::string> names;
-  if (vae_best_layout(d, names, P3D_VAE_KIND_ELBO, in, n_enc, enc_dims, latent, n_dec, dec_dims, out) > P3D_VAE_LDS_LIMIT)
-    return 0;
-  int xoff, toff, ldt, moff;
-  return (int64_t)vae_seq_layout(d, xoff, toff, ldt, moff);   // (both forms run one tile per workgroup)
-}
-
-extern "C" int p3d_vae_seq_set_form(p3d_vae* v, int32_t form) {
-  if (!v || (form != 0 && form != 1)) return fail(P3D_ERR_ARG, "p3d_vae_seq_set_form: form must be 0 or 1");
-  v->seq_form = form;
-  return P3D_OK;
-}
-
-extern "C" int p3d_vae_seq_filter(p3d_vae* v, const float* pred, const int64_t* seq_off, int64_t S, int64_t N,
-                                  const float* eps, uint64_t ctr, int64_t eps_row0, const float* target,
-                                  float* state, int32_t* started, float* ref, float* frame_err, double* seq_err,
-                                  void* stream) {
-  if (!v || !pred || !seq_off || !ref) return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: null argument");
-  if (v->kind != P3D_VAE_KIND_ELBO) return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: a bones filter has no sequence form");
-  if (v->wide || v->desc.in % v->desc.out != 0 || v->desc.in / v->desc.out > P3D_VAE_SEQ_MAX_LEN)
-    return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: in must be seq_len * out with seq_len in 1 .. " +
-                                 std::to_string(P3D_VAE_SEQ_MAX_LEN));
-  if (!v->seq_lds)
-    return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: parameters, one tile and the state tile exceed a workgroup's LDS");
-  if (S < 1 || S > (1 << 20)) return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: S must be in 1 .. 2^20");
-  if (N < 1 || N > (1 << 20)) return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: N must be in 1 .. 2^20");
-  if (eps_row0 < 0) return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: eps_row0 must be >= 0");
-  if ((state != nullptr) != (started != nullptr))
-    return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: state and started go together");
-  if ((frame_err || seq_err) && !target)
-    return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: frame_err and seq_err need a target");
-  for (const void* p : {(const void*)pred, (const void*)eps, (const void*)target, (const void*)state, (const void*)ref})
-    if ((uintptr_t)p % 16 != 0)
-      return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: pred, eps, target, state and ref must be 16-byte aligned");
-  VaeSeqArgs a{};
-  a.desc = v->desc; a.desc_dev = v->d_desc; a.pk = v->pk; a.pred = pred; a.seq_off = seq_off; a.S = S; a.N = N;
-  a.eps = eps; a.seed = v->seed; a.ctr = ctr; a.eps_row0 = eps_row0; a.target = target;
-  a.state = state; a.started = started; a.ref = ref; a.frame_err = frame_err; a.seq_err = seq_err;
-  a.seq_len = v->seq_len; a.xoff = v->seq_xoff; a.toff = v->seq_toff; a.ldt = v->seq_ldt; a.moff = v->seq_moff;
-  const unsigned grid = (unsigned)((S + 15) / 16);
-  if (v->seq_form == 0) hipLaunchKernelGGL(k_vae_seq, dim3(grid), dim3(64), v->seq_lds, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(k_vae_seq4, dim3(grid), dim3(256), v->seq_lds, (hipStream_t)stream, a);
-  LAUNCH_CHECK("k_vae_seq");
-  return P3D_OK;
-}
-
-extern "C" int64_t p3d_vae_workspace(const p3d_vae* v, int64_t B) {
-  if (!v || B < 1) return 0;
-  const int64_t nblk = (B + 63) / 64;
-  return (int64_t)sizeof(float) * (nblk * ((int64_t)v->desc.P + 4) + 4 + (v->wide ? 2 * B * v->n0 : 0));
-}
+// The VAE pose filter, its noise and its bones (include/p3d.h; kernels in p3d_vae*.h, p3d_bones.h)
+#include "p3d_vae_host.h"
 
 #include "p3d_dp.h"

@@ -1,6 +1,6 @@
 // p3d_bones.h -- joints <-> bones of the bones filter (gfx950): src/top_vae_3d_pose/bones.py:71-98
 // (convert_to_bones_tf), :101-121 (convert_to_bones) and :124-153 (convert_to_joints).  Device code
-// only; the host side is in p3d.hip.
+// only; the host side is in p3d_vae_host.h.
 //
 // The skeleton has joints 0 .. 16 with the hip, joint 0, at the origin; joint k >= 1 is columns
 // 3 (k - 1) .. 3 (k - 1) + 2 of a 48-vector.  Bone b runs from joint BJA[b] to joint BJB[b]

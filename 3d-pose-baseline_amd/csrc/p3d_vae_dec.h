@@ -1,12 +1,12 @@
 // p3d_vae_dec.h -- the VAE filters' decoder on its own (gfx950): VAE.decode of
 // src/top_vae_3d_pose/models.py:74-76, and poses drawn from the prior (z ~ N(0, I), the commented
-// gen_sample of models.py:55-59).  Device code only; the host side is in p3d.hip.
+// gen_sample of models.py:55-59).  Device code only; the host side is in p3d_vae_host.h.
 //
 // vae_layout packs the layers in order, so the decoder's parameters -- layers head + 1 .. nl - 1 --
 // are ONE contiguous range of the packed copy, from L[head + 1].wpk to Ppk.  Only that range goes
 // into LDS (the default filter: 4736 of 8960 packed floats), and behind it come four per-wave areas
 // that hold nothing but the z tile and the decoder's activations.  The host describes this in a
-// decoder-only VaeDesc (p3d.hip vae_dec_layout: wpk / bpk rebased to the range, ain / aout into the
+// decoder-only VaeDesc (p3d_vae_layout.h vae_dec_layout: wpk / bpk rebased to the range, ain / aout into the
 // shrunk area) that lives on the device beside the full one.
 //
 // A wave runs a 16-row tile through the decoder with vae_layer_fwd itself, layers and k-steps in

@@ -1,6 +1,6 @@
 // p3d_vae_noise.h -- the noise the VAE filters are trained to remove (gfx950), drawn on the device:
 // src/top_vae_3d_pose/data_handler.py:48-84 (add_noise) as a counter-based stream.  Device code
-// only; the host side (p3d_vae_add_noise) is in p3d.hip.
+// only; the host side (p3d_vae_add_noise) is in p3d_vae_host.h.
 //
 // Output row r is `width` contiguous floats of the table `src` [rows, d]: its row r, or -- the
 // window form -- the k = width / d rows from row starts[r] (clamped into [0, rows - k]).  With

@@ -1,6 +1,6 @@
 // p3d_vae_seq.h -- the temporal VAE filter run as a recurrence over whole sequences in ONE launch
 // (src/3d_pose_vae_filter_kin.py:285-361 evaluate(), gfx950).  Device code only; the host side is
-// in p3d.hip.
+// in p3d_vae_host.h.
 //
 // The filter reads the last seq_len = in / out poses concatenated; frame f's refined pose r_f is
 // written back into the buffer that feeds the next seq_len - 1 frames:
@@ -25,8 +25,7 @@
 // waits on another.
 #pragma once
 #include "p3d_vae.h"
-
-#define P3D_VAE_SEQ_MAX_LEN 5   // in / out
+#include "p3d_vae_desc.h"   // P3D_VAE_SEQ_MAX_LEN, VaeDesc
 
 struct VaeSeqArgs {
   VaeDesc desc;               // by value: kernel arguments are uniform and invariant, so the layers' dimensions

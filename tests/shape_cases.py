@@ -10,8 +10,8 @@ tests/test_gpu_vae_shapes.py run them on the device.
 
 expected_forward_tags / expected_backward_tags / serve_expected restate the dispatch conditions of
 csrc/p3d.hip (forward_gemv, use_big, out_part_ok, use_xchg, p3d_backward's `multi`, serve_shape_error)
-in the tags p3d_profile_start / p3d_profile_stop report.  vae_layout_bytes restates vae_layout's size
-formula, vae_layout_index vae_best_layout's three tries.
+in the tags p3d_profile_start / p3d_profile_stop report.  vae_layout_bytes restates the size formula
+of vae_layout (csrc/p3d_vae_layout.h), vae_layout_index vae_plan's three tries.
 """
 import numpy as np
 
@@ -250,7 +250,7 @@ VAE_LAYOUT = {
     "wide_edge": (0, 163712),
 }
 VAE_LDS_LIMIT = 163840
-VAE_TRIES = ((4, 1), (4, 0), (0, 0))           # (wpad, stage_x) in the order vae_best_layout tries them
+VAE_TRIES = ((4, 1), (4, 0), (0, 0))           # (wpad, stage_x) in the order vae_plan tries them
 # the sequence filter serves the entries whose input is a whole number of 48-wide frames and whose
 # layout leaves room for its state tile (p3d_vae_seq_lds_bytes > 0)
 VAE_SEQ_NAMES = ("nostagger_lat64", "nostagger_w96", "deep33_in96", "deep44", "deep44_small", "w128", "w136_edge")
@@ -294,7 +294,7 @@ def vae_layout_bytes(shape, wpad, stage_x):
 
 
 def vae_layout_index(shape):
-    """The first of vae_best_layout's three tries that fits the LDS limit (2 where none does)."""
+    """The first of vae_plan's three tries that fits the LDS limit (2 where none does)."""
     for i, (wpad, stage_x) in enumerate(VAE_TRIES):
         if vae_layout_bytes(shape, wpad, stage_x) <= VAE_LDS_LIMIT:
             return i

@@ -109,7 +109,8 @@ def _existing_shapes():
 
 
 def test_layout_formula_equals_the_library():
-    """vae_layout_bytes at the first try that fits == p3d_vae_lds_bytes, for every table entry and
+    """vae_layout_bytes at the first try that fits == p3d_vae_lds_bytes (vae_plan of
+    csrc/p3d_vae_layout.h, restated independently in shape_cases), for every table entry and
     every shape of the existing GPU tests; the table's indices and sizes are the recorded ones."""
     assert sorted(sc.VAE_LAYOUT) == sorted(sc.VAE_SHAPES)
     for name, shape in sc.VAE_SHAPES.items():
