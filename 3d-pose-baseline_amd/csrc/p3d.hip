@@ -1256,6 +1256,7 @@ static_assert(kServe6Rows == P3D_SERVE6_ROWS, "p3d_serve_plan.h plans for the sl
 #define SERVE_KERNEL_k_serve5(D, NDT, NCM, RT, PAIR) k_serve5<D, NDT, 2, 2>
 #define SERVE_KERNEL_k_serve6(D, NDT, NCM, RT, PAIR) k_serve6<D, NDT, NCM, RT, PAIR>
 #define SERVE_KERNEL_k_serve6_rounds(D, NDT, NCM, RT, PAIR) k_serve6_rounds<D, NDT, NCM, RT>
+#define SERVE_KERNEL_k_serve6_rounds_w4(D, NDT, NCM, RT, PAIR) k_serve6_rounds_w4<D, NDT, NCM, RT>
 #define SERVE_KERNEL_ROW(KIND, D, NDT, NCM, RT, PAIR) SERVE_KERNEL_##KIND(D, NDT, NCM, RT, PAIR),
 static void (*const kServeKernels[])(ServeArgs) = {P3D_SERVE_FORMS(SERVE_KERNEL_ROW)};
 #undef SERVE_KERNEL_ROW
@@ -1365,7 +1366,7 @@ static int serve_impl(p3d_model* m, const float* x, int64_t B, float* y, const f
     m->serve_choice = ch; m->serve_B = B; m->serve_with_loss = t != nullptr;
   }
   const ServeForm& f = *m->serve_choice.form;
-  const bool use6 = f.kind == SK_k_serve6 || f.kind == SK_k_serve6_rounds;
+  const bool use6 = serve_kind_is6(f.kind);
   a.split = m->serve_choice.S;
   a.nb = m->serve_choice.nb;   // batch-64 steps, or k_serve6's units of 16 RT rows
   a.ecg = m->serve_ecg;
@@ -1402,7 +1403,7 @@ static int serve_impl(p3d_model* m, const float* x, int64_t B, float* y, const f
   }
   ProfScope ps(m, "serve");
   HP(2);
-  go(ps, kServeKernels[&f - kServeForms], dim3((unsigned)m->serve_grid), dim3(f.kind == SK_k_serve ? 512 : 256), st, a);
+  go(ps, kServeKernels[&f - kServeForms], dim3((unsigned)m->serve_grid), dim3((unsigned)serve_kind_threads(f.kind)), st, a);
   HP(3);
   LAUNCH_CHECK("k_serve");
   return P3D_OK;

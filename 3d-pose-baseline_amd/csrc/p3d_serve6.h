@@ -48,6 +48,12 @@
 #ifndef P3D_S6_LATE_EPOCH
 #define P3D_S6_LATE_EPOCH 1        // the epoch read off the prologue's critical path (round 5)
 #endif
+#ifndef P3D_S6_HELPER_NAP
+#define P3D_S6_HELPER_NAP 8        // k_serve6_rounds: s_sleep between a helper wave's polls of the partials word (x 64 clocks)
+#endif
+#ifndef P3D_S6_HELPER_PRIO
+#define P3D_S6_HELPER_PRIO 2       // k_serve6_rounds: static s_setprio 1 for its helper waves (0 none, 1 the contraction waves; MEASUREMENTS 22)
+#endif
 
 
 // Timeline stamps for development (-DP3D_TRACE, tools/trace_serve6.py): for every group, its
@@ -131,13 +137,23 @@ __device__ __forceinline__ int p3d_tile_owner(int t, int n, int T) { return ((t 
 // code where the kernel itself has 512 + 256).
 template <int DEPTH, int NDT, int NCM, int RT = 4, bool PAIR = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_serve6(ServeArgs p) {
-  constexpr bool ROUNDS = false;
+  constexpr bool ROUNDS = false, HELPERS = false;
 #include "p3d_serve6_body.h"
 }
 
-// the pair form with its rounds run back to back: launches of more than one round per group
+// the pair form with its rounds run back to back: launches of more than one round per group.
+// Two waves per SIMD (p3d_serve6_helpers.h): waves 0-3 contract and never stop between blocks, waves
+// 4-7 do the work between contractions; one register allocation for both roles, 256 registers.
 template <int DEPTH, int NDT, int NCM, int RT>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_serve6_rounds(ServeArgs p) {
-  constexpr bool PAIR = true, ROUNDS = true;
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_serve6_rounds(ServeArgs p) {
+  constexpr bool PAIR = true, ROUNDS = true, HELPERS = true;
+#include "p3d_serve6_body.h"
+}
+
+// the same with one wave per SIMD, each doing its own boundary work (P3D_SERVE6_HELPERS=0): the form
+// the helper waves were measured against, and the yardstick of their tests
+template <int DEPTH, int NDT, int NCM, int RT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_serve6_rounds_w4(ServeArgs p) {
+  constexpr bool PAIR = true, ROUNDS = true, HELPERS = false;
 #include "p3d_serve6_body.h"
 }

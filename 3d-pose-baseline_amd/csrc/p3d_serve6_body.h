@@ -33,7 +33,10 @@
   // wave-uniform values the compiler cannot prove uniform (the wave index, everything read
   // from LDS) go through readfirstlane: they end in scalar registers, and
   // buffer loads with a scalar offset need no per-lane waterfall loop
-  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // (HELPERS: 512 threads -- waves 0-3 contract, waves 4-7 finish; wave 4 + w has wave w's K slice
+  // and tiles, so w is the slice of either role)
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(HELPERS ? (tid >> 6) & 3 : tid >> 6);
+  const int tidc = HELPERS ? (tid & 255) : tid;   // the constant copy's index (one copy per role)
 #if P3D_S6_PIN_ARGS
   // (round 5) every argument the prologue reads, fetched from the kernel-argument segment at once:
   // left to itself the compiler loaded them where they are used, several behind branches on earlier
@@ -83,6 +86,11 @@
     // build left it unset and such a workgroup advanced a word at a stale LDS offset)
     sh[5] = -1;
     sh[6] = 0;                               // PAIR: waves past their store drain (publish counter)
+    if constexpr (HELPERS) {
+      sh[7] = 0;                             // contraction waves that have written a block's partials (4 per block)
+      sh[8] = 0;                             // helper waves that have read a block's partials (4 per block)
+      sh[9] = 0;                             // helper waves at their own barrier (hbar)
+    }
     if (bad) __hip_atomic_store(p.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
   const int nl_ec = 2 * p.nblk + 1, tot_ec = nl_ec * ECT * 48;
@@ -149,7 +157,7 @@
     }
 #pragma unroll
     for (int k = 0; k < ECN; ++k) {
-      const int idx = tid + 256 * k, idc = idx < tot_ec ? idx : 0;
+      const int idx = tidc + 256 * k, idc = idx < tot_ec ? idx : 0;
       const int l = idc / (ECT * 48), rem = idc % (ECT * 48), cs = rem / 48, j = rem % 48;
       const float e = p.ecg[((int64_t)l * T + min(tlo + cs, T - 1)) * 48 + j];
       vec[k] = idx < tot_ec ? e : 0.f;
@@ -279,7 +287,7 @@
       // divisor -- copied from the table k_serve_prep forms once per parameter version
 #pragma unroll
     for (int k = 0; k < ECN; ++k)
-      if (tid + 256 * k < tot_ec) ec[tid + 256 * k] = vec[k];
+      if ((!HELPERS || tid < 256) && tidc + 256 * k < tot_ec) ec[tidc + 256 * k] = vec[k];
     if (tid < nl_ec) ecm[tid] = wq;
     __syncthreads();
   }
@@ -428,6 +436,28 @@
 #else
 #define P3D_S6_OSTAMP(k) do { } while (0)
 #endif
+  // HELPERS: a barrier of the four helper waves alone (the contraction waves never stop): each
+  // counts on sh[9] behind its own LDS traffic and polls, asleep between reads, until all four have.
+  // Bounded like every wait here.
+  unsigned hbn = 0;
+  auto hbar = [&]() {
+    hbn += 4;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (lane == 0) __hip_atomic_fetch_add(&sh[9], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    for (int spin = 0;; ++spin) {
+      const unsigned v = (unsigned)__builtin_amdgcn_readfirstlane(
+          __hip_atomic_load(&sh[9], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+      if (v >= hbn) break;
+      if (spin > P3D_SERVE_SPIN) {
+        broken = true;
+        sh[4] = 1;
+        if (lane == 0) __hip_atomic_store(p.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        break;
+      }
+      __builtin_amdgcn_s_sleep(1);
+    }
+    asm volatile("" ::: "memory");
+  };
   // (PAIR: both units' tiles, A's then B's, dealt over the members as one list)
   // (pre: out_wpre's fragments are in hand -- not at a round boundary of the ROUNDS form, where
   // the ring is live and every fragment is requested here)
@@ -435,6 +465,13 @@
     constexpr int OT = RT * NDT, OTT = PAIR ? 2 * OT : OT;
     const int o_lo = (OTT * r) / n, o_hi = (OTT * (r + 1)) / n;
     P3D_S6_OSTAMP(0);
+    // (HELPERS: the helper waves' K-slice partials in the odd blocks' red buffer, theirs while they
+    // hold back the "read" word of an odd block; their own barrier)
+    f32x4* const ro = HELPERS ? red + 4 * RT * NCM * 64 : red;
+    auto obar = [&]() {
+      if constexpr (HELPERS) hbar();
+      else __syncthreads();
+    };
     const __amdgpu_buffer_rsrc_t ryA = p3d_rsrc(act + 3 * slab), r4 = p3d_rsrc(lo.Wf);
     const __amdgpu_buffer_rsrc_t ryB = p3d_rsrc(act + (PAIR ? 7 : 3) * slab);
     for (int c0 = o_lo; c0 < o_hi; c0 += OCH) {
@@ -458,7 +495,8 @@
         // the K slice in halves of 8 k-groups, both halves' fragments requested before the first
         // MFMA (32 loads at L = 1024: the hidden rings are dead here; two 8-entry arrays stay in
         // registers where one 16-entry array went to scratch)
-        constexpr int GH = OGH;
+        // (HELPERS: halves of 4 -- 64 registers of fragments, not 128: one allocation for both roles)
+        constexpr int GH = HELPERS ? 4 : OGH;
         auto ld_half = [&](int gs, f32x4 (&av)[GH], f32x4 (&wv)[GH], bool wpre) {
 #pragma unroll
           for (int g = 0; g < GH; ++g) {
@@ -492,13 +530,13 @@
       }
 #pragma unroll
       for (int j = 0; j < OCH; ++j)
-        if (j < nt) red[(w * OCH + j) * 64 + lane] = oacc[j];   // (only the round's live tiles)
+        if (j < nt) ro[(w * OCH + j) * 64 + lane] = oacc[j];   // (only the round's live tiles)
       if (c0 == o_lo) P3D_S6_OSTAMP(1);
-      __syncthreads();
+      obar();
       if (w < nt) {                            // wave j sums tile j's four slices in slice order
         f32x4 sl[4];                           // (all four requested before the first add)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) sl[k] = red[(k * OCH + w) * 64 + lane];
+        for (int k = 0; k < 4; ++k) sl[k] = ro[(k * OCH + w) * 64 + lane];
         __builtin_amdgcn_sched_barrier(0);
         f32x4 tot = sl[0];
 #pragma unroll
@@ -512,7 +550,7 @@
           p3d_serve_loss_tile<!PAIR>(p, se, (orow >> 4) * NDT + tile, ((p.M + 15) >> 4) * NDT);
       }
       if (c0 == o_lo) P3D_S6_OSTAMP(2);
-      __syncthreads();                         // red is rewritten next (next round / phase)
+      obar();                                  // red is rewritten next (next round / phase)
     }
   };
 
@@ -818,6 +856,9 @@
 #endif
   // (ROUNDS: the prologue stands in front of the group's first round and the closing post / wait /
   // output phase behind its last, outside the loop of rounds: the same text as in the loop below)
+  if constexpr (HELPERS) {
+#include "p3d_serve6_helpers.h"
+  } else {
   if constexpr (ROUNDS) {
     if (gi < p.nb) {
       const int64_t rowA = (int64_t)gi * ROWS, rowB = (int64_t)(gi + ng) * ROWS;
@@ -1093,6 +1134,7 @@
       wait_for(nsync);                         // both units' last hidden layers (slabs 3, 7)
       out_phase(rowA, rowB, true);
     }
+  }
   }
   }
   if (tid == 0 && sh[5] >= 0)   // (every member has read the epoch by now: see its read)

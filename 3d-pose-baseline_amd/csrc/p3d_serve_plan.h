@@ -20,7 +20,9 @@
 // the narrow forms; 2 for 7 / 8 tiles (depth 4 spills there: 77 / 136 registers; depth 2 none / 38;
 // the 7-tile form with weights 4 ahead, 53 spills, is built for P3D_SERVE6_DEPTH=4); an 8-deep
 // weight ring measured 117 vs 107-112 us at RT = 10.  The pair form: two units of 5 row tiles per
-// group; k_serve6_rounds: the pair form on long launches, its rounds run back to back.
+// group; k_serve6_rounds: the pair form on long launches, its rounds run back to back, with helper
+// waves for the work between contractions (512 threads); k_serve6_rounds_w4: the same on one wave
+// per SIMD (P3D_SERVE6_HELPERS=0).
 #define P3D_SERVE_FORMS(X)                                                                      \
   X(k_serve, 2, 1, 0, 4, false) X(k_serve, 2, 2, 0, 4, false) X(k_serve, 2, 3, 0, 4, false)      \
   X(k_serve, 2, 4, 0, 4, false)                                                                 \
@@ -34,9 +36,15 @@
   X(k_serve6, 4, 3, 2, 1, false) X(k_serve6, 4, 3, 2, 2, false) X(k_serve6, 2, 3, 11, 2, false) \
   X(k_serve6, 4, 3, 2, 6, false) X(k_serve6, 4, 3, 2, 8, false) X(k_serve6, 4, 3, 2, 10, false) \
   X(k_serve6, 4, 3, 2, 12, false) X(k_serve6, 4, 3, 2, 16, false)                               \
-  X(k_serve6, 4, 3, 2, 5, true) X(k_serve6_rounds, 4, 3, 2, 5, true)
+  X(k_serve6, 4, 3, 2, 5, true) X(k_serve6_rounds, 4, 3, 2, 5, true)                             \
+  X(k_serve6_rounds_w4, 4, 3, 2, 5, true)
 
-enum ServeKind { SK_k_serve, SK_k_serve5, SK_k_serve6, SK_k_serve6_rounds };
+enum ServeKind { SK_k_serve, SK_k_serve5, SK_k_serve6, SK_k_serve6_rounds, SK_k_serve6_rounds_w4 };
+// (k_serve6 and both rounds kernels: the k_serve6 launch -- banks by epoch, no memset, its slabs)
+inline bool serve_kind_is6(ServeKind k) { return k == SK_k_serve6 || k == SK_k_serve6_rounds || k == SK_k_serve6_rounds_w4; }
+// threads per workgroup: k_serve splits K over 8 waves; k_serve6_rounds runs two waves per SIMD,
+// contraction waves and helper waves (p3d_serve6_helpers.h); every other form one wave per SIMD
+inline int serve_kind_threads(ServeKind k) { return k == SK_k_serve || k == SK_k_serve6_rounds ? 512 : 256; }
 
 struct ServeForm {
   ServeKind kind;
@@ -64,6 +72,7 @@ inline std::string serve_kernel_name(ServeKind kind, int depth, int ndt, int ncm
     case SK_k_serve: return "k_serve<" + dn + ", 4>";
     case SK_k_serve5: return "k_serve5<" + dn + ", 2, 2>";
     case SK_k_serve6_rounds: return "k_serve6_rounds<" + dn + cr + ">";
+    case SK_k_serve6_rounds_w4: return "k_serve6_rounds_w4<" + dn + cr + ">";
     default: return "k_serve6<" + dn + cr + (pair ? ", true>" : ">");
   }
 }
@@ -91,6 +100,8 @@ struct ServeKnobs {
   // launches of more than max_nb steps on the pair form with its rounds run back to back
   // (k_serve6_rounds) where the pair form's conditions hold (P3D_SERVE6_ROUNDS: 0 off -- k_serve5)
   int rounds = 1;
+  // the rounds form with helper waves (P3D_SERVE6_HELPERS: 0 -- one wave per SIMD, k_serve6_rounds_w4)
+  int helpers = 1;
 };
 
 inline ServeKnobs serve_knobs_from_env() {
@@ -103,6 +114,7 @@ inline ServeKnobs serve_knobs_from_env() {
   read("P3D_SERVE6_DEPTH", k.depth);
   read("P3D_SERVE6_PAIR", k.pair);
   read("P3D_SERVE6_ROUNDS", k.rounds);
+  read("P3D_SERVE6_HELPERS", k.helpers);
   return k;
 }
 
@@ -203,7 +215,8 @@ inline ServeChoice serve_plan(int L, int num_layers, int NDT, int cus, const Ser
       // (a forced k_serve6 -- P3D_SERVE6=2 -- whose plan is the pair form runs a long launch's rounds
       // back to back as well)
       const bool rounds = pair && long_launch && k.rounds && !with_loss;
-      c.form = serve_form_find(rounds ? SK_k_serve6_rounds : SK_k_serve6, depth, NDT, s.ncm, s.rt, pair);
+      const ServeKind kind = !rounds ? SK_k_serve6 : k.helpers ? SK_k_serve6_rounds : SK_k_serve6_rounds_w4;
+      c.form = serve_form_find(kind, depth, NDT, s.ncm, s.rt, pair);
       if (!c.form) { c.refused = "p3d_serve: the planned k_serve6 form is not built"; return c; }
       c.S = s.S;
       c.nb = (int)((B + 16 * s.rt - 1) / (16 * s.rt));   // units of 16 RT rows

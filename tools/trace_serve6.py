@@ -11,6 +11,10 @@ epilogue: the K-slice sums (LDS), the epilogue math + stores.
 A launch of more than 32 steps (k_serve6_rounds; P3D_SERVE6_PAIR=1 selects the pair form's columns)
 also prints "round_boundary": the first round's last blocks, the next round's input layers, the
 second round's first blocks and where the first round's output layer runs.
+With helper waves (the default k_serve6_rounds; P3D_SERVE6_HELPERS=0 selects the one-wave form) the
+stamps are contraction wave 0's: contraction start and end of every block are meaningful -- so are
+"ordinary_boundaries_us", the gap and the block contractions of "round_boundary" -- while the K-combine,
+epilogue, input-layer and output-layer columns belong to the helper waves and are not stamped.
 """
 import ctypes
 import json
