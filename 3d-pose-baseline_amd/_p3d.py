@@ -102,6 +102,8 @@ SIGNATURES = [
                                 c_int32, c_void_p]),
     ("p3d_unnormalize", c_int32, [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
                                   c_void_p, c_void_p]),
+    ("p3d_sample_world", c_int32, [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     ("p3d_lift", c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
                            c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     ("p3d_lift_sync", c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int32,

@@ -19,6 +19,7 @@
 #include "p3d_eval.h"
 #include "p3d_gemm.h"
 #include "p3d_data.h"
+#include "p3d_sample.h"
 #include "p3d_clip.h"
 #include "p3d_serve.h"
 #include "p3d_serve6.h"
@@ -2270,6 +2271,32 @@ extern "C" int p3d_unnormalize(const void* xn, int32_t in_dtype, int64_t F, int3
   if (in_dtype == P3D_DTYPE_F32) k_unnormalize<true><<<grid, 256, 0, (hipStream_t)stream>>>(xn, F, U, mean, stdv, dims_to_use, D, out);
   else k_unnormalize<false><<<grid, 256, 0, (hipStream_t)stream>>>(xn, F, U, mean, stdv, dims_to_use, D, out);
   LAUNCH_CHECK("k_unnormalize");
+  return 0;
+}
+
+// sample()'s numbers (src/predict_3dpose.py:512-546) for N rows in one launch: p3d_unnormalize,
+// + root, p3d_cam_transform(inverse = 1) with each row's camera, p3d_root_center -- the same bits.
+extern "C" int p3d_sample_world(const void* yn, int32_t in_dtype, int64_t N, int32_t U, const double* mean96,
+                                const double* std96, const int32_t* dims_to_use, const double* root,
+                                const double* cams, int32_t C, const int32_t* cam_of_row, double* out,
+                                void* stream) {
+  if (!yn || !mean96 || !std96 || !dims_to_use || !cams || !out)
+    return fail(P3D_ERR_ARG, "p3d_sample_world: null argument");
+  if (N < 1 || N > (1 << 20)) return fail(P3D_ERR_ARG, "p3d_sample_world: N must be in 1 .. 2^20");
+  if (U < 1 || U > P3D_SAMPLE_W) return fail(P3D_ERR_ARG, "p3d_sample_world: U must be in 1 .. 96");
+  if (C < 1 || C > P3D_SAMPLE_MAX_CAMS) return fail(P3D_ERR_ARG, "p3d_sample_world: C must be in 1 .. 64");
+  if (in_dtype != P3D_DTYPE_F32 && in_dtype != P3D_DTYPE_F64)
+    return fail(P3D_ERR_ARG, "p3d_sample_world: in_dtype F32 or F64");
+  if (!aligned16(out)) return fail(P3D_ERR_ARG, "p3d_sample_world: out must be 16-byte aligned");
+  if (((uintptr_t)root & 7) != 0) return fail(P3D_ERR_ARG, "p3d_sample_world: root must be 8-byte aligned");
+  SampleArgs a{yn, N, U, mean96, std96, dims_to_use, root, cams, C, cam_of_row, out};
+  const int64_t tiles = (N + P3D_SAMPLE_ROWS - 1) / P3D_SAMPLE_ROWS;
+  const dim3 grid((unsigned)(tiles < P3D_SAMPLE_MAX_BLOCKS ? tiles : P3D_SAMPLE_MAX_BLOCKS));
+  hipStream_t s = (hipStream_t)stream;
+  if (in_dtype == P3D_DTYPE_F64) k_sample_world<false, false><<<grid, 256, 0, s>>>(a);
+  else if (aligned16(yn)) k_sample_world<true, true><<<grid, 256, 0, s>>>(a);
+  else k_sample_world<true, false><<<grid, 256, 0, s>>>(a);
+  LAUNCH_CHECK("k_sample_world");
   return 0;
 }
 

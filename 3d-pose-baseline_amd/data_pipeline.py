@@ -185,6 +185,69 @@ def unnormalize(xn, mean, std, dims_to_use, D=None, out=None):
     return out
 
 
+SAMPLE_MAX_ROWS = 1 << 20     # rows of one p3d_sample_world call
+SAMPLE_MAX_CAMS = 64
+
+
+def _cam_of_row(cam_of_row, N, C):
+    """Per-row camera indices as a device int32 tensor.  Host indices are range-checked here; a
+    device int32 tensor is taken as already checked (as _dims)."""
+    torch = _torch()
+    if isinstance(cam_of_row, torch.Tensor) and cam_of_row.is_cuda and cam_of_row.dtype == torch.int32:
+        t = cam_of_row.reshape(-1).contiguous()
+    else:
+        c = np.asarray(cam_of_row.cpu() if isinstance(cam_of_row, torch.Tensor) else cam_of_row,
+                       np.int64).reshape(-1)
+        if c.size and (c.min() < 0 or c.max() >= C):
+            raise ValueError("sample_world: camera indices out of range [0, %d)" % C)
+        t = as_device(c.astype(np.int32), torch.int32)
+    if t.numel() != N:
+        raise ValueError("sample_world: cam_of_row has %d entries for %d rows" % (t.numel(), N))
+    return t
+
+
+def sample_world(yn, mean, std, dims_to_use, cams, cam_of_row=None, root=None, out=None):
+    """The numbers sample() shows (src/predict_3dpose.py:512-546) for N rows in one launch:
+    unNormalizeData, + root [N, 3] on every joint (when given), camera -> world with camera
+    cam_of_row[row] of cams [C, 21] (None: camera 0), minus the transformed root joint.
+    yn [N, U] float32 / float64 -> [N, 96] float64 on the device: the bits of unnormalize ->
+    + root -> camera_to_world -> root_center.  More than 2^20 rows are split into calls of 2^20
+    (rows are independent)."""
+    torch = _torch()
+    t = yn if isinstance(yn, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(yn))
+    if t.dtype not in (torch.float32, torch.float64):
+        t = t.to(torch.float64)
+    t = t.to(device=device(), non_blocking=True).contiguous()
+    if t.dim() != 2:
+        raise ValueError("sample_world: expected [N, U], got %s" % (tuple(t.shape),))
+    N = t.shape[0]
+    mean, std = as_device(mean).reshape(-1), as_device(std).reshape(-1)
+    if mean.numel() != 96 or std.numel() != 96:
+        raise ValueError("sample_world: mean/std must have 96 entries")
+    use = _dims(dims_to_use, 96, "sample_world")
+    if use.numel() != t.shape[1]:
+        raise ValueError("sample_world: %d columns for %d used dimensions" % (t.shape[1], use.numel()))
+    cm = as_device(cams).reshape(-1, CAM_DOUBLES)
+    C = cm.shape[0]
+    if C < 1 or C > SAMPLE_MAX_CAMS:
+        raise ValueError("sample_world: 1 .. %d cameras, got %d" % (SAMPLE_MAX_CAMS, C))
+    if cam_of_row is not None:
+        cam_of_row = _cam_of_row(cam_of_row, N, C)
+    if root is not None:
+        root = as_device(root)
+        if tuple(root.shape) != (N, 3):
+            raise ValueError("sample_world: root must be [%d, 3], got %s" % (N, tuple(root.shape)))
+    out = _out(out, (N, 96), t.device, "sample_world")
+    code = _p3d.P3D_DTYPE_F32 if t.dtype == torch.float32 else _p3d.P3D_DTYPE_F64
+    for s in range(0, N, SAMPLE_MAX_ROWS):
+        e = min(N, s + SAMPLE_MAX_ROWS)
+        check(lib().p3d_sample_world(ptr(t[s:e]), code, e - s, use.numel(), ptr(mean), ptr(std), ptr(use),
+                                     ptr(root[s:e]) if root is not None else 0, ptr(cm), C,
+                                     ptr(cam_of_row[s:e]) if cam_of_row is not None else 0, ptr(out[s:e]),
+                                     _stream()), "p3d_sample_world")
+    return out
+
+
 def moments(x):
     """(mean, population std) over axis 0 of [F, D] float64."""
     torch = _torch()

@@ -12,6 +12,10 @@ the epoch ``train`` loop (:188-334), ``get_action_subset`` (:337-349) and
 * ``evaluate_action_wise`` shards each action's batches across the ranks of a
   ``torch.distributed`` job and combines per-action sums with one RCCL
   all-reduce (SURVEY.md 8e);
+* ``sample`` (:447-612) computes the numbers the reference draws -- all test sequences in one
+  forward sweep, un-normalised, with ``--camera_frame`` taken to root-centred world coordinates
+  by one fused launch per tensor -- and returns them (``--sample_dir`` writes the rows the
+  reference would show); the matplotlib figure itself is not built;
 * the H3.6M tree and cameras.h5 are read as the reference's HDF5 files (h5py) or as .npz
   archives of the same datasets under the same paths (``load_data``); ``--synthetic`` feeds
   data of the reference's shapes without files.
@@ -74,6 +78,9 @@ def build_parser():
     p.add_argument("--max_batch", type=int, default=8192,
                    help="rows the device workspaces hold (evaluation submits up to this many rows per "
                         "launch); front ends stepping single frames can pass their batch size")
+    p.add_argument("--sample_dir", type=str, default="",
+                   help="--sample: directory that receives samples.npz, the rows the reference would "
+                        "draw (empty: not written)")
     p.add_argument("--device_loop", type=int, default=1,
                    help="1: stage each epoch in HBM and train without per-step host round trips; "
                         "0: the reference's per-batch step() loop")
@@ -345,27 +352,31 @@ def dp_epoch_share(enc, dec, rank, world):
 SUBJECT_IDS = [1, 5, 6, 7, 8, 9, 11]
 
 
-def load_data(flags):
+def load_data(flags, with_roots=False):
     """The training / test sets and their statistics (src/predict_3dpose.py:194-208): cameras,
     3D poses (camera frame, root-centred, normalised) and the 2D inputs -- ground-truth
     projections or Stacked Hourglass detections.  ``--data_dir`` / ``--cameras_path`` name the
     H3.6M tree and cameras.h5 or their .npz archives (data_utils, cameras); ``--synthetic``
-    skips the files."""
+    skips the files.  ``with_roots`` (sample(), :452-463) also keeps ``train_root_positions``,
+    ``test_root_positions`` and the cameras ``rcams``; the synthetic set has none."""
     if flags.synthetic:
         return synthetic_h36m(out_dim=42 if flags.predict_14 else 48, seed=flags.seed)
     actions = data_utils.define_actions(flags.action)
     rcams = cameras.load_cameras(flags.cameras_path, SUBJECT_IDS)
-    (train_set_3d, test_set_3d, data_mean_3d, data_std_3d, dim_to_ignore_3d, dim_to_use_3d, _,
-     _) = data_utils.read_3d_data(actions, flags.data_dir, flags.camera_frame, rcams, flags.predict_14)
+    (train_set_3d, test_set_3d, data_mean_3d, data_std_3d, dim_to_ignore_3d, dim_to_use_3d, train_roots,
+     test_roots) = data_utils.read_3d_data(actions, flags.data_dir, flags.camera_frame, rcams, flags.predict_14)
     if flags.use_sh:
         two = data_utils.read_2d_predictions(actions, flags.data_dir)
     else:
         two = data_utils.create_2d_data(actions, flags.data_dir, rcams)
     train_set_2d, test_set_2d, data_mean_2d, data_std_2d, dim_to_ignore_2d, dim_to_use_2d = two
-    return dict(train_set_2d=train_set_2d, train_set_3d=train_set_3d, test_set_2d=test_set_2d,
-                test_set_3d=test_set_3d, data_mean_3d=data_mean_3d, data_std_3d=data_std_3d,
-                dim_to_use_3d=dim_to_use_3d, dim_to_ignore_3d=dim_to_ignore_3d, data_mean_2d=data_mean_2d,
-                data_std_2d=data_std_2d, dim_to_use_2d=dim_to_use_2d, dim_to_ignore_2d=dim_to_ignore_2d)
+    d = dict(train_set_2d=train_set_2d, train_set_3d=train_set_3d, test_set_2d=test_set_2d,
+             test_set_3d=test_set_3d, data_mean_3d=data_mean_3d, data_std_3d=data_std_3d,
+             dim_to_use_3d=dim_to_use_3d, dim_to_ignore_3d=dim_to_ignore_3d, data_mean_2d=data_mean_2d,
+             data_std_2d=data_std_2d, dim_to_use_2d=dim_to_use_2d, dim_to_ignore_2d=dim_to_ignore_2d)
+    if with_roots:
+        d.update(train_root_positions=train_roots, test_root_positions=test_roots, rcams=rcams)
+    return d
 
 
 def train(flags=None):
@@ -475,11 +486,152 @@ def train(flags=None):
     return model
 
 
+N_CAMERAS = 4
+N_SAMPLES = 15      # the poses sample() draws (src/predict_3dpose.py:590)
+
+
+def sample_camera(rcams, key3d):
+    """The camera a camera-frame sequence was taken with (src/predict_3dpose.py:529-536): of the
+    subject's four cameras the one named ``sname.split('.')[1]``.  Returns (index 0..3, camera
+    tuple); a name none of the four carries raises ValueError, as the reference's list.index."""
+    subj, _, sname = key3d
+    cname = sname.split('.')[1]
+    names = [rcams[(subj, c + 1)][-1] for c in range(N_CAMERAS)]
+    if cname not in names:
+        raise ValueError("sample: no camera named %r among subject %s's cameras %s" % (cname, subj, names))
+    idx = names.index(cname)
+    return idx, rcams[(subj, idx + 1)]
+
+
+def pick_rows(n_last, nsamples=N_SAMPLES):
+    """The rows sample() draws (src/predict_3dpose.py:575-609): a np.random.permutation of the
+    LAST key's rows, of which the plot loop shows entries 1 .. nsamples (exidx starts at 1, so
+    entry 0 is never shown).  Fewer than nsamples + 1 rows: as many as idx[1:] has."""
+    idx = np.random.permutation(n_last)
+    return idx[1:1 + nsamples]
+
+
+def sample_rows(model, X, Y, stats, world=None):
+    """sample()'s device work over all rows at once: the eval forward of X [N, 32] in chunks of
+    model.max_batch rows, the inputs un-normalised, and targets Y [N, U3] and predictions either
+    un-normalised (world None) or taken to root-centred world coordinates by one p3d_sample_world
+    launch each; ``world`` = (cams [C, 21], cam_of_row [N] int32, root [N, 3]) on the device.
+    Returns (enc_in [N, 64], dec_out [N, 96], poses3d [N, 96]) float64; no host sync."""
+    import data_pipeline as dp
+    torch = model.torch
+    N = X.shape[0]
+    P = torch.empty((N, model.output_size), dtype=torch.float32, device=model.device)
+    for s in range(0, N, model.max_batch):
+        e = min(N, s + model.max_batch)
+        model.forward_device(X[s:e], False, 1.0, out=P[s:e])
+    enc_in = dp.unnormalize(X, stats["data_mean_2d"], stats["data_std_2d"], stats["dim_to_use_2d"], 64)
+    mean3, std3 = dp.as_device(stats["data_mean_3d"]), dp.as_device(stats["data_std_3d"])
+    use3 = dp._dims(stats["dim_to_use_3d"], 96, "sample")
+    if world is None:
+        return enc_in, dp.unnormalize(Y, mean3, std3, use3, 96), dp.unnormalize(P, mean3, std3, use3, 96)
+    cams_dev, cam_of_row, root = world
+    # the root goes back onto the targets only (src/predict_3dpose.py:526): on the predictions it
+    # would cancel in exact arithmetic, not in float64
+    dec_out = dp.sample_world(Y, mean3, std3, use3, cams_dev, cam_of_row, root=root)
+    poses3d = dp.sample_world(P, mean3, std3, use3, cams_dev, cam_of_row, root=None)
+    return enc_in, dec_out, poses3d
+
+
+def sample(flags=None):
+    """The numbers behind src/predict_3dpose.py:447-577 (the drawing, :579-612, is not built):
+    the lifter over every test sequence, inputs, targets and predictions un-normalised, and with
+    --camera_frame targets and predictions taken to world coordinates and re-centred on the root
+    joint.  All test sequences are one upload, one forward sweep and one p3d_sample_world launch
+    per tensor.  Returns {"keys", "seq_off", "enc_in" [N, 64], "dec_out" [N, 96], "poses3d"
+    [N, 96]} (device float64 tensors, rows in test_set_2d.keys() order, key i at
+    seq_off[i]:seq_off[i + 1]) and "picked", the rows the reference would draw (host numpy).
+    With --sample_dir the picked rows are written to <sample_dir>/samples.npz."""
+    from top_vae_3d_pose import data_handler
+    import data_pipeline as dp
+    flags = flags or FLAGS
+    if flags.synthetic and flags.camera_frame:
+        raise ValueError("--sample --synthetic --camera_frame: the synthetic set has no cameras or root "
+                         "positions to return to world coordinates with")
+    actions = data_utils.define_actions(flags.action)
+    d = load_data(flags, with_roots=True)
+    print("done reading and normalizing data.")
+    test_set_2d, test_set_3d = d["test_set_2d"], d["test_set_3d"]
+    keys = list(test_set_2d.keys())
+    if not keys:
+        raise ValueError("sample: the test set is empty")
+    key3ds, lens = [], []
+    for key2d in keys:
+        key3d = data_handler.get_key3d(key2d, camera_frame=flags.camera_frame)
+        n2d, n3d = test_set_2d[key2d].shape[0], test_set_3d[key3d].shape[0]
+        if n2d != n3d:
+            raise ValueError("sample: key %r has %d 2D rows but its 3D key %r has %d" % (key2d, n2d, key3d, n3d))
+        key3ds.append(key3d)
+        lens.append(n2d)
+    seq_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    N = int(seq_off[-1])
+    if N < 1:
+        raise ValueError("sample: the test sequences hold no rows")
+    cam_table, cam_of_seq = None, None
+    if flags.camera_frame:
+        # one table of the test subjects' cameras; each sequence's entry in it
+        rcams, slot, packed = d["rcams"], {}, []
+        cam_of_seq = np.zeros(len(keys), np.int64)
+        for i, key3d in enumerate(key3ds):
+            idx, cam = sample_camera(rcams, key3d)
+            if (key3d[0], idx) not in slot:
+                slot[(key3d[0], idx)] = len(packed)
+                packed.append(dp.pack_camera(*cam[:6]))
+            cam_of_seq[i] = slot[(key3d[0], idx)]
+        cam_table = np.stack(packed)
+    with Session() as sess:
+        print("Creating %d layers of %d units." % (flags.num_layers, flags.linear_size))
+        model = create_model(sess, actions, 128, flags)      # (batch_size = 128, :470)
+        print("Model loaded")
+        torch = model.torch
+        for subj, b, fname in keys:
+            print("Subject: {}, action: {}, fname: {}".format(subj, b, fname))
+        with torch.cuda.device(model.device):
+            X = torch.from_numpy(_stack([test_set_2d[k] for k in keys], model.input_size)).to(model.device)
+            Y = torch.from_numpy(_stack([test_set_3d[k] for k in key3ds], model.output_size)).to(model.device)
+            stats = {k: d[k] for k in ("data_mean_2d", "data_std_2d", "dim_to_use_2d", "data_mean_3d",
+                                       "data_std_3d", "dim_to_use_3d")}
+            world = None
+            if flags.camera_frame:
+                roots = d["test_root_positions"]
+                root = dp.as_device(np.concatenate([np.asarray(roots[k], np.float64) for k in key3ds]))
+                cam_of_row = torch.repeat_interleave(
+                    dp.as_device(cam_of_seq.astype(np.int32), torch.int32),
+                    dp.as_device(np.asarray(lens, np.int64), torch.int64), output_size=N)
+                world = (dp.as_device(cam_table), cam_of_row, root)
+            enc_in, dec_out, poses3d = sample_rows(model, X, Y, stats, world)
+            # the reference draws after its loop over the keys: its arrays are the last key's (:575-577)
+            lo = int(seq_off[-2])
+            idx = pick_rows(int(seq_off[-1]) - lo)
+            rows = torch.from_numpy(idx.astype(np.int64) + lo).to(model.device)
+            picked = {"key": keys[-1], "idx": idx,
+                      "enc_in": enc_in.index_select(0, rows).cpu().numpy(),
+                      "dec_out": dec_out.index_select(0, rows).cpu().numpy(),
+                      "poses3d": poses3d.index_select(0, rows).cpu().numpy()}
+            model.check_errors()
+    out = {"keys": keys, "seq_off": seq_off, "enc_in": enc_in, "dec_out": dec_out, "poses3d": poses3d,
+           "picked": picked}
+    if getattr(flags, "sample_dir", ""):
+        os.makedirs(flags.sample_dir, exist_ok=True)
+        np.savez(os.path.join(flags.sample_dir, "samples.npz"), key=np.array([str(v) for v in picked["key"]]),
+                 idx=picked["idx"], enc_in=picked["enc_in"], dec_out=picked["dec_out"], poses3d=picked["poses3d"])
+    return out
+
+
 def main(argv=None):
     global FLAGS
     FLAGS = build_parser().parse_args(argv)
     if FLAGS.sample:
-        raise NotImplementedError("sample() is matplotlib visualisation (out of scope for this build)")
+        out = sample(FLAGS)
+        where = (os.path.join(FLAGS.sample_dir, "samples.npz") if FLAGS.sample_dir
+                 else "the returned dict (pass --sample_dir to write them)")
+        print("The matplotlib drawing is not built; the {0} rows it would show are in {1}".format(
+            len(out["picked"]["idx"]), where))
+        return out
     try:
         return train(FLAGS)
     finally:

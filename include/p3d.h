@@ -413,6 +413,24 @@ int p3d_unnormalize(const void* xn, int32_t in_dtype, int64_t F, int32_t U, cons
                     const double* stdv, const int32_t* dims_to_use, int32_t D, double* out,
                     void* stream);
 
+/* The numbers behind sample(), src/predict_3dpose.py:512-546, for N rows in one launch.  Per row,
+ * in float64 with every product and sum rounded on its own:
+ *   1. scatter yn's U values (P3D_DTYPE_F32, or F64 rounded to float32) into 96 zeros;
+ *   2. * std96 + mean96 (unNormalizeData, :512-514);
+ *   3. + the row's root on all 32 joints, when root [N, 3] is given (:526; NULL: skipped);
+ *   4. R^T X + T per joint with camera cam_of_row[row] of cams [C, 21] (:539; NULL: camera 0);
+ *   5. minus the transformed joint 0 on every joint (:542).
+ * out [N, 96] holds the bits of p3d_unnormalize -> + root -> p3d_cam_transform(inverse = 1) ->
+ * p3d_root_center without their intermediates.  1 <= N <= 2^20, 1 <= U <= 96, 1 <= C <= 64; out
+ * 16-byte aligned, root 8-byte aligned (else P3D_ERR_ARG, before any GPU work).  dims_to_use
+ * entries are in 0..95 and cam_of_row entries in 0..C-1: the caller checks them (an entry of
+ * dims_to_use outside 0..95 is dropped; a camera index outside 0..C-1 gives undefined values
+ * in that row).  Asynchronous on stream and capturable. */
+int p3d_sample_world(const void* yn, int32_t in_dtype, int64_t N, int32_t U, const double* mean96,
+                     const double* std96, const int32_t* dims_to_use, const double* root,
+                     const double* cams, int32_t C, const int32_t* cam_of_row, double* out,
+                     void* stream);
+
 /* src/openpose_3dpose_sandbox.py:347-356 per call (normalize_data of the mapped 2D rows, the
  * float32 placeholder cast, model.step at is_training False / keep 1, unNormalizeData): raw
  * [B, D2] float64 -> out [B, D3] float64.  U2 / U3 must equal the model's input / output size.
