@@ -26,7 +26,7 @@ import numpy as np
 
 import predict_3dpose
 from top_vae_3d_pose import data_handler, losses, models
-from top_vae_3d_pose.args_def import ENVIRON as ENV
+from top_vae_3d_pose.args_def import ENVIRON as ENV, filter_samples
 
 _spec = importlib.util.spec_from_file_location(
     "pose_vae_filter", os.path.join(os.path.dirname(os.path.abspath(__file__)), "3d_pose_vae_filter.py"))
@@ -78,6 +78,7 @@ def train(argv=None, read_from_config=False):
         raise NotImplementedError("--train_all is not built: the lifter stays frozen")
     if f.sample:
         raise NotImplementedError("--sample (gen_sample_img) is matplotlib visualisation, not built")
+    K = filter_samples(f)      # the test block's VAE output: None, one draw; else the mean of K samples
     if f.use_effb1:
         print("--use_effb1 is accepted and ignored: the features are read precomputed from", f.effnet_outputs_path)
     optimizer = base.get_optimizer()
@@ -116,7 +117,8 @@ def train(argv=None, read_from_config=False):
         for step in range(nbt):
             sl = slice(step * B, (step + 1) * B)
             xb, yb, fb = Xt[sl], Yt[sl], Ft[sl]
-            out_3d, out_vae = model(xb, effnet_output=fb, training=False)
+            out_3d, out_vae = (model(xb, effnet_output=fb, training=False) if K is None else
+                               model(xb, effnet_output=fb, training=False, samples=K))
             lt[step].copy_(losses.ELBO.compute_loss(model.vae, model.segments(xb, out_3d, fb), yb))
             a, b = losses.ELBO.compute_error_3d_vs_vae(yb, out_3d, out_vae)
             e3.append(a)

@@ -19,7 +19,7 @@ import numpy as np
 
 import predict_3dpose
 from top_vae_3d_pose import losses, models
-from top_vae_3d_pose.args_def import ENVIRON as ENV
+from top_vae_3d_pose.args_def import ENVIRON as ENV, filter_samples
 
 
 class Adam(object):
@@ -98,6 +98,7 @@ def train(argv=None, read_from_config=False):
         raise NotImplementedError("--train_all is not built: the lifter stays frozen")
     if f.sample:
         raise NotImplementedError("--sample (gen_sample_img) is matplotlib visualisation, not built")
+    K = filter_samples(f)      # the test block's VAE output: None, one draw; else the mean of K samples
     pose3d, lf = _lifter(f)
     d = predict_3dpose.load_data(lf)
     model = models.Pose3DVae(latent_dim=f.latent_dim, enc_dim=f.enc_dim, dec_dim=f.dec_dim, pose3d=pose3d,
@@ -124,7 +125,7 @@ def train(argv=None, read_from_config=False):
         e3, ev = [], []
         for step in range(nb):
             xb, yb = X[step * B:(step + 1) * B], Y[step * B:(step + 1) * B]
-            out_3d, out_vae = model(xb, training=False)
+            out_3d, out_vae = model(xb, training=False) if K is None else model(xb, training=False, samples=K)
             lt[step].copy_(losses.ELBO.compute_loss(model.vae, out_3d, yb))
             a, b = losses.ELBO.compute_error_3d_vs_vae(yb, out_3d, out_vae)
             e3.append(a)

@@ -28,7 +28,7 @@ import numpy as np
 
 import predict_3dpose
 from top_vae_3d_pose import data_handler, losses, models
-from top_vae_3d_pose.args_def import ENVIRON as ENV
+from top_vae_3d_pose.args_def import ENVIRON as ENV, filter_samples
 
 SEQ_LEN = 3
 MAX_FRAMES = 1 << 20      # p3d_vae_seq_filter's N per call
@@ -67,6 +67,7 @@ def train(argv=None, read_from_config=False):
     print((len(data_train["starts"]), SEQ_LEN, size), (len(data_train["starts"]), size))
     print((len(data_test["starts"]), SEQ_LEN, size), (len(data_test["starts"]), size))
     B = f.batch_size
+    K = filter_samples(f)
     model = models.VAE(SEQ_LEN * size, latent_dim=f.latent_dim, enc_dim=f.enc_dim, dec_dim=f.dec_dim,
                        human_3d_size=size, max_batch=max(B, 4096), seed=f.seed)
     optimizer = base.get_optimizer()
@@ -112,7 +113,7 @@ def train(argv=None, read_from_config=False):
         for step in range(nb_te):
             xb, yb = X_te[step * B:(step + 1) * B], Y_te[step * B:(step + 1) * B]
             lt[step].copy_(losses.ELBO.compute_loss(model, xb, yb))
-            preds = model(xb, training=False)
+            preds = model(xb, training=False) if K is None else model(xb, training=False, samples=K)
             errs["pred_error"].append(losses.ELBO.compute_pred_error(yb, preds))
             errs["error_34"].append(losses.ELBO.compute_pred_error(xb[:, size:2 * size], yb))
             errs["error_3_pred"].append(losses.ELBO.compute_pred_error(xb[:, size:2 * size], preds))
@@ -137,9 +138,12 @@ def evaluate(argv=None, read_from_config=False, eps_ctr=1):
     """The recurrent evaluation of 3d_pose_vae_filter_kin.py:285-361.  Returns a dict: per_key
     {key2d: (err 2d-3d, err vae)}, overall (the two means over all frames), noise (mean, std, min,
     max of the per-frame lifter error), and -- for whoever wants to check them -- the device
-    tensors pred, target, ref, frame_err, the offsets seq_off and the eps counter used."""
+    tensors pred, target, ref, frame_err, the offsets seq_off and the eps counter used.
+    With --filter_samples K > 1 every frame's refined pose is the mean of K samples (draw k at eps
+    counter eps_ctr + k); the dict then also holds ref_var and per_key_var {key2d: mean of ref_var}."""
     import torch
     f = ENV.setup(read_from_config=read_from_config, argv=argv)
+    K = filter_samples(f)
     base = _base()
     pose3d, lf = base._lifter(f)
     d = predict_3dpose.load_data(lf)
@@ -164,6 +168,7 @@ def evaluate(argv=None, read_from_config=False, eps_ctr=1):
     target = torch.from_numpy(np.concatenate(ys)).to(dev)
     pred = pose3d.serve_device(X)                       # the lifter once over all test frames
     ref = torch.empty_like(pred)
+    ref_var = None if K is None else torch.empty_like(pred)
     frame_err = torch.empty((N, 2), dtype=torch.float32, device=dev)
     seq_err = torch.empty((len(keys2d), 2), dtype=torch.float64, device=dev)
     a = 0
@@ -174,7 +179,12 @@ def evaluate(argv=None, read_from_config=False, eps_ctr=1):
         lo, hi = int(seq_off[a]), int(seq_off[b])
         if hi - lo > MAX_FRAMES:
             raise ValueError("evaluate: sequence %s has more than %d frames" % (keys2d[a], MAX_FRAMES))
-        if hi > lo:
+        if hi > lo and K is not None:
+            o = vae.filter_sequences(pred[lo:hi], seq_off[a:b + 1] - lo, ctr=eps_ctr, eps_row0=lo, target=target[lo:hi],
+                                     want=("ref", "ref_var", "frame_err", "seq_err"), samples=K)
+            ref[lo:hi], frame_err[lo:hi], seq_err[a:b] = o["ref"], o["frame_err"], o["seq_err"]
+            ref_var[lo:hi] = o["ref_var"]
+        elif hi > lo:
             o = vae.filter_sequences(pred[lo:hi], seq_off[a:b + 1] - lo, ctr=eps_ctr, eps_row0=lo, target=target[lo:hi],
                                      want=("ref", "frame_err", "seq_err"))
             ref[lo:hi], frame_err[lo:hi], seq_err[a:b] = o["ref"], o["frame_err"], o["seq_err"]
@@ -182,12 +192,16 @@ def evaluate(argv=None, read_from_config=False, eps_ctr=1):
             seq_err[a:b] = 0
         a = b
     se = seq_err.cpu().numpy()
-    per_key = {}
+    per_key, per_key_var = {}, {}
     for i, key2d in enumerate(keys2d):
         print("Subject: {}, action: {}, fname: {}".format(*key2d))
         m = se[i] / max(int(lens[i]), 1)
         per_key[key2d] = (float(m[0]), float(m[1]))
         print("Err 2d-3d: {}, VAE: {}".format(m[0], m[1]))
+        if K is not None:      # how much of a refined coordinate is the draw: the mean variance over the K samples
+            lo, hi = int(seq_off[i]), int(seq_off[i + 1])
+            per_key_var[key2d] = float(ref_var[lo:hi].double().mean()) if hi > lo else 0.0
+            print("VAE sample variance ({} samples): {}".format(K, per_key_var[key2d]))
     overall = tuple(float(v) for v in se.sum(axis=0) / max(N, 1))
     print("Pred error 2d to 3d:", overall[0])
     print("Pred error vae filter:", overall[1])
@@ -196,7 +210,8 @@ def evaluate(argv=None, read_from_config=False, eps_ctr=1):
     for v in noise:
         print(v)
     pose3d.check_errors()
-    return {"per_key": per_key, "overall": overall, "noise": noise, "pred": pred, "target": target, "ref": ref,
+    extra = {} if K is None else {"ref_var": ref_var, "per_key_var": per_key_var, "samples": K}
+    return {**extra, "per_key": per_key, "overall": overall, "noise": noise, "pred": pred, "target": target, "ref": ref,
             "frame_err": frame_err, "seq_off": seq_off, "keys": keys2d, "eps_ctr": eps_ctr, "vae": vae, "pose3d": pose3d}
 
 

@@ -180,6 +180,13 @@ SIGNATURES = [
     ("p3d_vae_decode", c_int32, [c_void_p, c_void_p, c_int64, c_uint64, c_int64, c_void_p, c_void_p, c_void_p]),
     ("p3d_vae_dec_lds_bytes", c_int64, [c_int32, c_int32, POINTER(c_int32), c_int32, c_int32]),
     ("p3d_vae_dec_set_grid", c_int32, [c_void_p, c_int32]),
+    ("p3d_vae_forward_mc", c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_uint64, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p]),
+    ("p3d_vae_forward_mc_cat", c_int32, [c_void_p, POINTER(P3DVaeCat), c_int64, c_int32, c_void_p, c_uint64, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("p3d_vae_seq_filter_mc", c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_uint64,
+                                        c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p]),
 ]
 
 

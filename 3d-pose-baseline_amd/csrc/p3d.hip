@@ -46,6 +46,7 @@
 #include "p3d_vae_wide.h"
 #include "p3d_vae_noise.h"
 #include "p3d_vae_dec.h"
+#include "p3d_vae_mc.h"
 
 // =====================================================================================
 // host side

@@ -579,6 +579,98 @@ extern "C" int p3d_vae_seq_filter(p3d_vae* v, const float* pred, const int64_t* 
                     stream, a);
 }
 
+namespace {
+
+// What the K-sample calls refuse before anything else, without a filter (and without a GPU): a null
+// output, K out of range, the device counter.
+int vae_mc_check(const void* out, const char* out_name, int32_t K, uint64_t ctr, const char* what) {
+  const std::string w(what);
+  if (!out) return fail(P3D_ERR_ARG, w + ": " + out_name + " is null");
+  if (K < 1 || K > P3D_VAE_MC_MAX_K)
+    return fail(P3D_ERR_ARG, w + ": K must be in 1 .. " + std::to_string(P3D_VAE_MC_MAX_K));
+  if (ctr == P3D_CTR_GLOBAL_STEP)
+    return fail(P3D_ERR_ARG, w + ": draw k uses the counter ctr + k (ctr may not be P3D_CTR_GLOBAL_STEP)");
+  return P3D_OK;
+}
+
+int vae_mc_bones(const p3d_vae* v, const char* what) {
+  if (v->plan.shape.kind != P3D_VAE_KIND_ELBO)
+    return fail(P3D_ERR_ARG, std::string(what) + ": a bones filter's outputs are lengths and direction cosines, "
+                                                 "and direction cosines do not average");
+  return P3D_OK;
+}
+
+int vae_forward_mc(p3d_vae* v, const float* x, const VaeCat* cat, int64_t B, int32_t K, const float* eps, uint64_t ctr,
+                   float* y_mean, float* y_var, float* mean, float* log_var, void* stream, const char* what) {
+  const hipStream_t st = (hipStream_t)stream;
+  VaeWideArgs wa{};
+  if (v->plan.wide)
+    if (int rc = vae_wide_fwd(v, x, cat, B, 0, wa, st, what)) return rc;
+  VaeMcArgs a{};
+  a.a = vae_args(v, x, nullptr, B, eps, ctr);
+  a.a.y = y_mean; a.a.mean = mean; a.a.log_var = log_var;
+  if (cat) a.a.cat = *cat;
+  a.y_var = y_var; a.K = K;
+  const int64_t nwg = (B + 63) / 64;
+  const int grid = (int)(nwg < v->cus ? nwg : v->cus);
+  return vae_launch(v, vae_kernel_index(VF_FWDMC, P3D_VAE_KIND_ELBO, cat != nullptr, 0, 4), grid, st, a);
+}
+
+}  // namespace
+
+extern "C" int p3d_vae_forward_mc(p3d_vae* v, const float* x, int64_t B, int32_t K, const float* eps, uint64_t ctr,
+                                  float* y_mean, float* y_var, float* mean, float* log_var, void* stream) {
+  if (int rc = vae_mc_check(y_mean, "y_mean", K, ctr, "p3d_vae_forward_mc")) return rc;
+  if (int rc = vae_check_call(v, x, B, "p3d_vae_forward_mc")) return rc;
+  if (int rc = vae_mc_bones(v, "p3d_vae_forward_mc")) return rc;
+  return vae_forward_mc(v, x, nullptr, B, K, eps, ctr, y_mean, y_var, mean, log_var, stream, "p3d_vae_forward_mc");
+}
+
+extern "C" int p3d_vae_forward_mc_cat(p3d_vae* v, const p3d_vae_cat* cat, int64_t B, int32_t K, const float* eps,
+                                      uint64_t ctr, float* y_mean, float* y_var, float* mean, float* log_var,
+                                      void* stream) {
+  if (int rc = vae_mc_check(y_mean, "y_mean", K, ctr, "p3d_vae_forward_mc_cat")) return rc;
+  VaeCat k;
+  if (int rc = vae_cat_call(v, cat, B, "p3d_vae_forward_mc_cat", &k)) return rc;
+  if (int rc = vae_mc_bones(v, "p3d_vae_forward_mc_cat")) return rc;
+  return vae_forward_mc(v, nullptr, &k, B, K, eps, ctr, y_mean, y_var, mean, log_var, stream, "p3d_vae_forward_mc_cat");
+}
+
+extern "C" int p3d_vae_seq_filter_mc(p3d_vae* v, const float* pred, const int64_t* seq_off, int64_t S, int64_t N,
+                                     int32_t K, const float* eps, uint64_t ctr, int64_t eps_row0, const float* target,
+                                     float* state, int32_t* started, float* ref, float* ref_var, float* frame_err,
+                                     double* seq_err, void* stream) {
+  const char* what = "p3d_vae_seq_filter_mc";
+  if (int rc = vae_mc_check(ref, "ref", K, ctr, what)) return rc;
+  if (!v || !pred || !seq_off) return fail(P3D_ERR_ARG, "p3d_vae_seq_filter_mc: null argument");
+  const VaePlan& p = v->plan;
+  if (int rc = vae_mc_bones(v, what)) return rc;
+  if (p.wide || p.desc.in % p.desc.out != 0 || p.desc.in / p.desc.out > P3D_VAE_SEQ_MAX_LEN)
+    return fail(P3D_ERR_ARG, "p3d_vae_seq_filter_mc: in must be seq_len * out with seq_len in 1 .. " +
+                                 std::to_string(P3D_VAE_SEQ_MAX_LEN));
+  if (!p.seq_lds)
+    return fail(P3D_ERR_ARG, "p3d_vae_seq_filter_mc: parameters, one tile and the state tile exceed a workgroup's LDS");
+  if (S < 1 || S > (1 << 20)) return fail(P3D_ERR_ARG, "p3d_vae_seq_filter_mc: S must be in 1 .. 2^20");
+  if (N < 1 || N > (1 << 20)) return fail(P3D_ERR_ARG, "p3d_vae_seq_filter_mc: N must be in 1 .. 2^20");
+  if (eps_row0 < 0) return fail(P3D_ERR_ARG, "p3d_vae_seq_filter_mc: eps_row0 must be >= 0");
+  if ((state != nullptr) != (started != nullptr))
+    return fail(P3D_ERR_ARG, "p3d_vae_seq_filter_mc: state and started go together");
+  if ((frame_err || seq_err) && !target)
+    return fail(P3D_ERR_ARG, "p3d_vae_seq_filter_mc: frame_err and seq_err need a target");
+  for (const void* q : {(const void*)pred, (const void*)eps, (const void*)target, (const void*)state, (const void*)ref,
+                        (const void*)ref_var})
+    if ((uintptr_t)q % 16 != 0)
+      return fail(P3D_ERR_ARG, "p3d_vae_seq_filter_mc: pred, eps, target, state, ref and ref_var must be 16-byte aligned");
+  VaeSeqMcArgs m{};
+  VaeSeqArgs& a = m.s;
+  a.desc = p.desc; a.desc_dev = v->d_desc; a.pk = v->pk; a.pred = pred; a.seq_off = seq_off; a.S = S; a.N = N;
+  a.eps = eps; a.seed = v->seed; a.ctr = ctr; a.eps_row0 = eps_row0; a.target = target;
+  a.state = state; a.started = started; a.ref = ref; a.frame_err = frame_err; a.seq_err = seq_err;
+  a.seq_len = p.seq_len; a.xoff = p.seq_xoff; a.toff = p.seq_toff; a.ldt = p.seq_ldt; a.moff = p.seq_moff;
+  m.ref_var = ref_var; m.K = K;
+  return vae_launch(v, vae_kernel_index(VF_SEQMC, P3D_VAE_KIND_ELBO, 0, 0, 4), (unsigned)((S + 15) / 16), stream, m);
+}
+
 extern "C" int64_t p3d_vae_workspace(const p3d_vae* v, int64_t B) {
   return v && B >= 1 ? (int64_t)sizeof(float) * v->plan.ws_floats(B) : 0;
 }

@@ -12,10 +12,11 @@
 #include <vector>
 
 // ---- the built kernels, each written down once: X(kernel, family, kind, cat, dx, waves, lds) ----
-// family: the forward, the loss / gradient / training step, the decoder alone, the sequence filter.
+// family: the forward, the loss / gradient / training step, the decoder alone, the sequence filter,
+// and the forward and the sequence filter averaged over K samples (p3d_vae_mc.h).
 // cat: the input comes through a VaeCat; dx: the wide form's core, which also leaves d loss / d input;
 // waves per workgroup; lds: which of a plan's sizes is the launch's dynamic LDS.
-enum VaeFamily { VF_FWD, VF_STEP, VF_DEC, VF_SEQ };
+enum VaeFamily { VF_FWD, VF_STEP, VF_DEC, VF_SEQ, VF_FWDMC, VF_SEQMC };
 enum VaeLdsOf { VL_FULL, VL_DEC, VL_SEQ };
 #define P3D_VAE_KERNELS(X)                                                                      \
   X(k_vae_fwd, FWD, ELBO, 0, 0, 4, FULL) X(k_vae_fwd_cat, FWD, ELBO, 1, 0, 4, FULL)             \
@@ -25,7 +26,9 @@ enum VaeLdsOf { VL_FULL, VL_DEC, VL_SEQ };
   X(k_vae_bones_step, STEP, BONES, 0, 0, 4, FULL) X(k_vae_bones_step_cat, STEP, BONES, 1, 0, 4, FULL) \
   X(k_vae_bones_step_dx, STEP, BONES, 0, 1, 4, FULL)                                            \
   X(k_vae_dec, DEC, ELBO, 0, 0, 4, DEC) X(k_vae_bones_dec, DEC, BONES, 0, 0, 4, DEC)            \
-  X(k_vae_seq, SEQ, ELBO, 0, 0, 1, SEQ) X(k_vae_seq4, SEQ, ELBO, 0, 0, 4, SEQ)
+  X(k_vae_seq, SEQ, ELBO, 0, 0, 1, SEQ) X(k_vae_seq4, SEQ, ELBO, 0, 0, 4, SEQ)                \
+  X(k_vae_fwd_mc, FWDMC, ELBO, 0, 0, 4, FULL) X(k_vae_fwd_mc_cat, FWDMC, ELBO, 1, 0, 4, FULL)   \
+  X(k_vae_seq4_mc, SEQMC, ELBO, 0, 0, 4, SEQ)
 
 struct VaeKernelRow {
   const char* name;
@@ -42,7 +45,9 @@ static constexpr int vae_kernel_index(int family, int kind, int cat, int dx, int
   return family == VF_FWD ? 2 * kind + cat
        : family == VF_STEP ? 4 + 3 * kind + (dx ? 2 : cat)
        : family == VF_DEC ? 10 + kind
-                          : 12 + (waves == 4);
+       : family == VF_SEQ ? 12 + (waves == 4)
+       : family == VF_FWDMC ? 14 + cat
+                            : 16;
 }
 static constexpr bool vae_kernels_in_index_order() {
   for (int i = 0; i < kVaeKernelCount; ++i) {
@@ -51,7 +56,7 @@ static constexpr bool vae_kernels_in_index_order() {
   }
   return true;
 }
-static_assert(kVaeKernelCount == 14 && vae_kernels_in_index_order(), "P3D_VAE_KERNELS is not in vae_kernel_index's order");
+static_assert(kVaeKernelCount == 17 && vae_kernels_in_index_order(), "P3D_VAE_KERNELS is not in vae_kernel_index's order");
 
 // ---- the shape ----------------------------------------------------------------------------------
 struct VaeShape {

@@ -27,7 +27,7 @@ import sys
 
 import predict_3dpose
 from top_vae_3d_pose import bones, losses, models
-from top_vae_3d_pose.args_def import ENVIRON as ENV
+from top_vae_3d_pose.args_def import ENVIRON as ENV, filter_samples
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -66,6 +66,9 @@ def train(argv=None, read_from_config=False):
     lists loss_train, loss_test (4-vectors), error_3d_out and error_vae_out."""
     import torch
     f = ENV.setup(read_from_config=read_from_config, argv=argv)
+    if filter_samples(f) is not None:
+        raise NotImplementedError("--filter_samples above 1 is not served by the bones filter: its outputs are lengths "
+                                  "and direction cosines, and direction cosines do not average")
     if f.train_all:
         raise NotImplementedError("--train_all is not built: the lifter stays frozen")
     if f.sample:

@@ -72,7 +72,20 @@ def build_parser():
     p.add_argument("--samples_dir", type=str, default="",
                    help="vae_filter.py: write each epoch's sample set (real, noised, predicted poses) to "
                         "DIR/samples_<epoch>.npz; empty (the default): off")
+    # build-specific: the VAE output of the test blocks (and of --evaluate's recurrence) as the mean of K
+    # posterior samples formed inside one launch (VAE.forward_device / filter_sequences, samples=K)
+    p.add_argument("--filter_samples", type=int, default=1,
+                   help="Posterior samples averaged into the VAE output at test time (1, the default: one draw, "
+                        "as the reference)")
     return p
+
+
+def filter_samples(flags):
+    """--filter_samples checked: None at 1 (the callers then call what they call without the flag), else K."""
+    k = int(getattr(flags, "filter_samples", 1))
+    if not 1 <= k <= 64:
+        raise ValueError("--filter_samples must be in 1 .. 64, got %d" % k)
+    return None if k == 1 else k
 
 
 class _ENV(object):

@@ -212,10 +212,65 @@ class VAE(object):
         return (ctypes.c_float * self.N_TERMS)(*[float(f) for f in factors])
 
     # ------------------------------------------------------------------ device entry points
-    def forward_device(self, x, eps=None, ctr=0, target=None, want=("y",)):
-        """One k_vae_fwd launch; returns a dict with the tensors named in `want` out of 'y',
-        'mean', 'log_var', 'z' and, with a target, 'row_terms' [B, 3]."""
+    MAX_SAMPLES = 64     # the library's bound on K
+
+    def _samples(self, samples, what):
+        if self.BONES:
+            raise NotImplementedError("%s: a bones filter's outputs are lengths and direction cosines, and direction "
+                                      "cosines do not average (samples is not served)" % what)
+        K = int(samples)
+        if K != samples or not 1 <= K <= self.MAX_SAMPLES:
+            raise ValueError("%s: samples must be an integer in 1 .. %d, got %r" % (what, self.MAX_SAMPLES, samples))
+        return K
+
+    def _eps_k(self, eps, K, rows):
+        """The caller's K draws as one contiguous [K, rows, latent] device tensor."""
         torch = self.torch
+        t = eps if isinstance(eps, torch.Tensor) else torch.from_numpy(np.array(eps, dtype=np.float32, order="C"))
+        if tuple(t.shape) != (K, rows, self.latent_dim):
+            raise ValueError("eps: expected shape [%d, %d, %d], got %s" % (K, rows, self.latent_dim, tuple(t.shape)))
+        if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
+            t = t.to(device=self.device, dtype=torch.float32).contiguous()
+        return t
+
+    def _forward_mc(self, x, K, eps, ctr, want):
+        """One k_vae_fwd_mc launch: the mean ('y') and, if asked, the variance ('y_var') of K samples."""
+        torch = self.torch
+        widths = {"y": self.output_size, "y_var": self.output_size, "mean": self.latent_dim, "log_var": self.latent_dim}
+        unknown = [k for k in want if k not in widths]
+        if unknown:
+            raise ValueError("forward_device: with samples the outputs are 'y', 'y_var', 'mean' and 'log_var', not %s"
+                             % unknown)
+        cat = None
+        if isinstance(x, list):
+            cat, B, _keep = self._cat(x)
+        else:
+            x = self._dev(x, self.input_size, "vae input")
+            B = x.shape[0]
+        eps = None if eps is None else self._eps_k(eps, K, B)
+        out = {k: torch.empty((B, widths[k]), dtype=torch.float32, device=self.device) for k in want}
+        y = out["y"] if "y" in out else torch.empty((B, self.output_size), dtype=torch.float32, device=self.device)
+        fn, what, xin = ((lib().p3d_vae_forward_mc, "p3d_vae_forward_mc", ptr(x)) if cat is None else
+                         (lib().p3d_vae_forward_mc_cat, "p3d_vae_forward_mc_cat", ctypes.byref(cat)))
+        check(fn(self._h, xin, B, K, ptr(eps), int(ctr), ptr(y), ptr(out.get("y_var")), ptr(out.get("mean")),
+                 ptr(out.get("log_var")), self.stream()), what)
+        return out
+
+    def forward_device(self, x, eps=None, ctr=0, target=None, want=("y",), samples=None):
+        """One k_vae_fwd launch; returns a dict with the tensors named in `want` out of 'y',
+        'mean', 'log_var', 'z' and, with a target, 'row_terms' [B, 3].
+
+        samples=K (1 .. 64): one k_vae_fwd_mc launch that runs the encoder once and the decoder on K
+        draws; 'y' is the mean of the K outputs and `want` may name 'y_var' (their variance),
+        'mean' and 'log_var'.  eps is [K, B, latent]; without it draw k is the library's stream at
+        counter ctr + k.  'z' and a target are not served with samples."""
+        torch = self.torch
+        if samples is not None:
+            K = self._samples(samples, "forward_device")
+            if target is not None or "z" in want:
+                raise ValueError("forward_device: with samples there is no single z and no loss term "
+                                 "('z' and target are not served)")
+            return self._forward_mc(x, K, eps, ctr, want)
         cat = None
         if isinstance(x, list):     # [seg, ...]: the concatenation is formed inside the kernels
             cat, B, _keep = self._cat(x)
@@ -309,7 +364,7 @@ class VAE(object):
                 torch.zeros((int(S),), dtype=torch.int32, device=self.device))
 
     def filter_sequences(self, pred, seq_off, eps=None, ctr=None, eps_row0=0, target=None, state=None,
-                         want=("ref",)):
+                         want=("ref",), samples=None):
         """The temporal filter run as the reference's evaluate() recurrence over whole sequences in
         one k_vae_seq launch: frame f's refined pose feeds the windows of the next seq_len - 1.
 
@@ -320,9 +375,15 @@ class VAE(object):
         eps [N, latent], or None for the library's Philox stream at (ctr, eps_row0 + frame index);
         ctr=None draws a fresh counter.  state is a new_seq_state() pair, updated in place.
         Returns a dict with the entries of `want` out of 'ref' [N, out], 'frame_err' [N, 2]
-        {err_pred, err_ref} and 'seq_err' [S, 2] (float64); the last two need a target."""
+        {err_pred, err_ref} and 'seq_err' [S, 2] (float64); the last two need a target.
+
+        samples=K (1 .. 64): one k_vae_seq4_mc launch in which frame f's refined pose is the mean of
+        K samples (forward_device's samples) and that mean is what feeds the next windows; `want`
+        may add 'ref_var' [N, out], eps is [K, N, latent], and without eps draw k uses counter
+        ctr + k (a fresh ctr advances the call counter by K)."""
         torch = self.torch
         self._seq_len()
+        K = None if samples is None else self._samples(samples, "filter_sequences")
         pred = self._dev(pred, self.human_3d_size, "pred")
         N = pred.shape[0]
         if isinstance(seq_off, torch.Tensor) and seq_off.is_cuda:
@@ -342,13 +403,16 @@ class VAE(object):
                                  % (N, h[0], h[-1]))
             off = torch.from_numpy(h).to(self.device)
         S = off.shape[0] - 1
-        eps = None if eps is None else self._dev(eps, self.latent_dim, "eps")
-        if eps is not None and eps.shape[0] != N:
+        if K is not None:
+            eps = None if eps is None else self._eps_k(eps, K, N)
+        else:
+            eps = None if eps is None else self._dev(eps, self.latent_dim, "eps")
+        if K is None and eps is not None and eps.shape[0] != N:
             raise ValueError("eps: expected %d rows, got %d" % (N, eps.shape[0]))
         target = None if target is None else self._dev(target, self.human_3d_size, "target")
         if target is not None and target.shape[0] != N:
             raise ValueError("target: expected %d rows, got %d" % (N, target.shape[0]))
-        unknown = [k for k in want if k not in ("ref", "frame_err", "seq_err")]
+        unknown = [k for k in want if k not in ("ref", "frame_err", "seq_err") + (("ref_var",) if K else ())]
         if unknown:
             raise ValueError("filter_sequences: unknown outputs %s" % unknown)
         if target is None and ("frame_err" in want or "seq_err" in want):
@@ -361,9 +425,11 @@ class VAE(object):
                     or not st.is_contiguous() or not started.is_contiguous()):
                 raise ValueError("state: expected the (float32 [%d, %d], int32 [%d]) pair of new_seq_state" % (S, w, S))
         if ctr is None:
-            self._calls += 1
-            ctr = self._calls
+            ctr = self._calls + 1
+            self._calls += K or 1
         out = {"ref": torch.empty((N, self.human_3d_size), dtype=torch.float32, device=self.device)}
+        if "ref_var" in want:
+            out["ref_var"] = torch.empty((N, self.human_3d_size), dtype=torch.float32, device=self.device)
         if "frame_err" in want:
             out["frame_err"] = torch.empty((N, 2), dtype=torch.float32, device=self.device)
         if "seq_err" in want:
@@ -371,6 +437,11 @@ class VAE(object):
         if N == 0:
             if "seq_err" in out:
                 out["seq_err"].zero_()
+        elif K is not None:
+            check(lib().p3d_vae_seq_filter_mc(self._h, ptr(pred), ptr(off), S, N, K, ptr(eps), int(ctr), int(eps_row0),
+                                              ptr(target), ptr(st), ptr(started), ptr(out["ref"]),
+                                              ptr(out.get("ref_var")), ptr(out.get("frame_err")),
+                                              ptr(out.get("seq_err")), self.stream()), "p3d_vae_seq_filter_mc")
         else:
             check(lib().p3d_vae_seq_filter(self._h, ptr(pred), ptr(off), S, N, ptr(eps), int(ctr), int(eps_row0),
                                            ptr(target), ptr(st), ptr(started), ptr(out["ref"]),
@@ -430,7 +501,13 @@ class VAE(object):
         """Workgroups of the decoder's launch per CU (0: the library's default).  Same bits either way."""
         check(lib().p3d_vae_dec_set_grid(self._h, int(wgs_per_cu)), "p3d_vae_dec_set_grid")
 
-    def __call__(self, inputs, training=False, eps=None):
+    def __call__(self, inputs, training=False, eps=None, samples=None):
+        """samples=K: the mean of K posterior samples (forward_device); the call counter advances by K."""
+        if samples is not None:
+            K = self._samples(samples, type(self).__name__)
+            ctr = self._calls + 1
+            self._calls += K
+            return self.forward_device(inputs, eps=eps, ctr=ctr, samples=K)["y"]
         self._calls += 1
         return self.forward_device(inputs, eps=eps, ctr=self._calls)["y"]
 
@@ -466,7 +543,9 @@ class VAEBones(VAE):
             raise ValueError("VAEBones: human_3d_size must be %d (16 bones), got %s" % (HUMAN_3D_SIZE, human_3d_size))
         super(VAEBones, self).__init__(input_size, latent_dim, enc_dim, dec_dim, human_3d_size, **kw)
 
-    def __call__(self, inputs, training=False, eps=None):
+    def __call__(self, inputs, training=False, eps=None, samples=None):
+        if samples is not None:
+            self._samples(samples, "VAEBones")      # raises NotImplementedError
         self._calls += 1
         y = self.forward_device(inputs, eps=eps, ctr=self._calls)["y"]
         return y[:, :16], y[:, 16:]
@@ -507,10 +586,12 @@ class Pose3DVae(object):
         self.vae = VAE(HUMAN_3D_SIZE, latent_dim, enc_dim, dec_dim, max_batch=max_batch, seed=seed,
                        device=pose3d.device.index)
 
-    def __call__(self, inputs, effnet_output=None, training=False, eps=None):
+    def __call__(self, inputs, effnet_output=None, training=False, eps=None, samples=None):
         if effnet_output is not None:
             raise NotImplementedError("Pose3DVae: effnet_output is taken by Pose3DVaeCat")
         out_3d = self.pose3d.serve_device(inputs)      # raises ValueError on a bad shape
+        if samples is not None:
+            return out_3d, self.vae(out_3d, training=training, eps=eps, samples=samples)
         return out_3d, self.vae(out_3d, training=training, eps=eps)
 
     def save_weights(self, path):
@@ -569,12 +650,15 @@ class Pose3DVaeCat(object):
             raise ValueError("%s: effnet_output given to a model built without use_effnet_ouptut" % type(self).__name__)
         return segs
 
-    def __call__(self, inputs, effnet_output=None, training=False, eps=None):
+    def __call__(self, inputs, effnet_output=None, training=False, eps=None, samples=None):
         torch = self.vae.torch
         if not isinstance(inputs, torch.Tensor):
             inputs = torch.from_numpy(np.array(inputs, dtype=np.float32, order="C"))
         inputs = inputs.to(device=self.vae.device, dtype=torch.float32).contiguous()
         out_3d = self.pose3d.serve_device(inputs)      # raises ValueError on a bad shape
+        if samples is not None:
+            return out_3d, self.vae(self.segments(inputs, out_3d, effnet_output), training=training, eps=eps,
+                                    samples=samples)
         self.vae._calls += 1
         y = self.vae.forward_device(self.segments(inputs, out_3d, effnet_output), eps=eps, ctr=self.vae._calls)["y"]
         return out_3d, y
@@ -619,8 +703,10 @@ class Pose3DVaeBones(object):
         """The lifter's output as bones in float32 arithmetic (convert_to_bones_tf), one launch."""
         return bones.convert_to_bones(out_3d, precise=False, out=out)
 
-    def __call__(self, inputs, effnet_output=None, training=False, eps=None):
+    def __call__(self, inputs, effnet_output=None, training=False, eps=None, samples=None):
         torch = self.vae.torch
+        if samples is not None:
+            self.vae._samples(samples, "Pose3DVaeBones")      # raises NotImplementedError
         if not isinstance(inputs, torch.Tensor):
             inputs = torch.from_numpy(np.array(inputs, dtype=np.float32, order="C"))
         inputs = inputs.to(device=self.vae.device, dtype=torch.float32).contiguous()

@@ -22,7 +22,7 @@ import sys
 
 import predict_3dpose
 from top_vae_3d_pose import data_handler, losses, models, samples
-from top_vae_3d_pose.args_def import ENVIRON as ENV
+from top_vae_3d_pose.args_def import ENVIRON as ENV, filter_samples
 
 
 def _base():
@@ -46,6 +46,7 @@ def train(argv=None, read_from_config=False):
     model.data_train and model.data_test."""
     import torch
     f = ENV.setup(read_from_config=read_from_config, argv=argv)
+    K = filter_samples(f)      # the test block's VAE output: None, one draw; else the mean of K samples
     if f.noised_sample:
         raise NotImplementedError("--noised_sample (gen_sample_img) is matplotlib visualisation, not built; "
                                   "--samples_dir DIR writes the sample sets it would draw")
@@ -88,7 +89,8 @@ def train(argv=None, read_from_config=False):
         for step, (x_noised, x_truth) in enumerate(data_test):
             lt[step].copy_(losses.ELBO.compute_loss(model, x_noised, x_truth))
             err_n.append(losses.ELBO.compute_pred_error(x_noised, x_truth))
-            err_p.append(losses.ELBO.compute_pred_error(model(x_noised, training=False), x_truth))
+            pred = model(x_noised, training=False) if K is None else model(x_noised, training=False, samples=K)
+            err_p.append(losses.ELBO.compute_pred_error(pred, x_truth))
         hist["loss_test"].append(lt[:nb].double().mean(dim=0).cpu().numpy())
         hist["error_noised"].append(float(torch.stack(err_n).mean().item()) if err_n else float("nan"))
         hist["error_pred"].append(float(torch.stack(err_p).mean().item()) if err_p else float("nan"))

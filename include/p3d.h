@@ -758,6 +758,56 @@ int p3d_vae_seq_set_form(p3d_vae* v, int32_t form);
 int64_t p3d_vae_seq_lds_bytes(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent,
                               int32_t n_dec, const int32_t* dec_dims, int32_t out, int32_t form);
 
+/* The filter averaged over K posterior samples inside ONE launch (k_vae_fwd_mc / k_vae_fwd_mc_cat /
+ * k_vae_seq4_mc, csrc/p3d_vae_mc.h): the encoder runs once per row, the decoder K times on the tile
+ * that is already in LDS, and the statistics are folded in registers.  For a row with encoder
+ * outputs mean, log_var and K draws eps_k, sample k is
+ *
+ *   y_k = decoder(eps_k * exp(0.5 log_var) + mean)
+ *
+ * in exactly p3d_vae_forward's arithmetic: with the caller's eps [K, B, latent], y_k has the bits
+ * p3d_vae_forward writes for eps_k = eps[k]; with eps null, draw k uses the library's stream at
+ * counter ctr + k (same seed, same site, row r of the call) and is the y of
+ * p3d_vae_forward(..., eps = null, ctr + k).  Per output element, in float32 with every operation
+ * rounded once and no division on the device:
+ *
+ *   m = y_0;  M = 0
+ *   for k = 1 .. K - 1:   d = y_k - m;   m = m + d * c_k;   M = M + d * (y_k - m)
+ *   y_mean = m            y_var = M * c_{K-1}            c_j = (float)(1.0 / (double)(j + 1))
+ *
+ * (y_var is the population variance of the K samples.)  K = 1 gives y_mean = y_0 bit for bit and
+ * y_var = 0.  mean, log_var [B, latent] and y_var [B, out] are written when non-null.  B up to 2^20;
+ * a wide filter needs B <= max_batch, as at p3d_vae_forward.  Asynchronous, capturable.
+ * P3D_ERR_ARG ("p3d_vae_forward_mc: ..."), without touching the GPU: a null handle, a null y_mean,
+ * K outside 1 .. 64, ctr == P3D_CTR_GLOBAL_STEP, and a bones filter: its outputs are lengths and
+ * direction cosines, and direction cosines do not average. */
+int p3d_vae_forward_mc(p3d_vae* v, const float* x, int64_t B, int32_t K,
+                       const float* eps /* [K, B, latent] or null */, uint64_t ctr,
+                       float* y_mean, float* y_var /* or null */,
+                       float* mean, float* log_var /* or null */, void* stream);
+/* The same with the segments in place of x: the bits of the plain call on the materialised
+ * concatenation. */
+int p3d_vae_forward_mc_cat(p3d_vae* v, const p3d_vae_cat* cat, int64_t B, int32_t K,
+                           const float* eps /* [K, B, latent] or null */, uint64_t ctr,
+                           float* y_mean, float* y_var /* or null */,
+                           float* mean, float* log_var /* or null */, void* stream);
+/* p3d_vae_seq_filter with r_f = the mean of K samples, fed back frame by frame inside the launch:
+ *
+ *   per frame f: buffer = buffer[1:] + [p_f];  (r_f, v_f) = (y_mean, y_var) of the K samples of
+ *                VAE(concat(buffer)) as defined above;  buffer[-1] = r_f
+ *
+ * eps is [K, N, latent] (draw k of frame g at eps[k][g]), or null: draw k is the stream
+ * p3d_vae_eps(seed, ctr + k, eps_row0, N, ...) gives.  ref [N, out] receives r_f, ref_var [N, out]
+ * (or null) v_f; err_ref / seq_err are taken of r_f.  Row r of frame f has the bits of
+ * p3d_vae_forward_mc on the same input and eps rows; K = 1 has the bits of p3d_vae_seq_filter.
+ * state / started chunk a stream as there: chunks give the bits of one call.  The four-wave form
+ * only.  P3D_ERR_ARG as above (a null ref for y_mean) and whatever p3d_vae_seq_filter refuses. */
+int p3d_vae_seq_filter_mc(p3d_vae* v, const float* pred, const int64_t* seq_off, int64_t S, int64_t N,
+                          int32_t K, const float* eps /* [K, N, latent] or null */, uint64_t ctr, int64_t eps_row0,
+                          const float* target, float* state, int32_t* started,
+                          float* ref, float* ref_var /* [N, out] or null */,
+                          float* frame_err, double* seq_err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
