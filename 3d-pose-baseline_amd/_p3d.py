@@ -118,6 +118,18 @@ SIGNATURES = [
     ("p3d_clip_lift", c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
                                 c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_int64, c_void_p]),
+    ("p3d_clips_workspace", c_int64, [c_int64, c_int64]),
+    ("p3d_clips_prepare", c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p,
+                                    c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    ("p3d_clips_finish", c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64,
+                                   c_void_p]),
+    ("p3d_clips_lift_workspace", c_int64, [c_int64, c_int64, c_int32, c_int32, c_int32]),
+    ("p3d_clips_lift", c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_uint64, c_int64,
+                                 c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32,
+                                 c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                 c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_int64, c_void_p]),
     ("p3d_moments_workspace", c_int64, [c_int64, c_int32]),
     ("p3d_moments", c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     ("p3d_crc32c", c_uint32, [c_void_p, c_int64, c_uint32]),

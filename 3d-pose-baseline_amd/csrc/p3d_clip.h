@@ -72,16 +72,17 @@ __device__ __forceinline__ void clip_last_kept(bool kept0, bool kept1, int& src0
   first = min(f0, f1);
 }
 
-// The carry: for every column c < ncols with need[c] != 0, the nearest chunk j < k whose mask has
-// bit c, into found[c] (-1: none).  Whole workgroup; smask: 256 words of LDS; need / found in LDS.
+// The carry: for every column c < ncols with need[c] != 0, the nearest chunk j in lo .. k - 1
+// whose mask has bit c, into found[c] (-1: none).  (lo: 0 for the single clip; a clip's first
+// chunk in a batch, p3d_clips.h.)  Whole workgroup; smask: 256 words of LDS; need / found in LDS.
 // The masks were written by an earlier launch.
-__device__ __forceinline__ void clip_lookback(const unsigned long long* __restrict__ mask, int k, int ncols,
+__device__ __forceinline__ void clip_lookback(const unsigned long long* __restrict__ mask, int k, int lo, int ncols,
                                               const int* need, int* found, unsigned long long* smask) {
   const int t = threadIdx.x;
   if (t < ncols) found[t] = need[t] ? -2 : -1;
-  for (int base = k - 1; base >= 0; base -= P3D_CLIP_THREADS) {
+  for (int base = k - 1; base >= lo; base -= P3D_CLIP_THREADS) {
     const int j = base - t;
-    smask[t] = j >= 0 ? mask[j] : 0ull;
+    smask[t] = j >= lo ? mask[j] : 0ull;
     __syncthreads();
     int pending = 0;
     if (t < ncols && found[t] == -2) {
@@ -179,15 +180,16 @@ __device__ __forceinline__ void clip_load_map(const ClipInArgs& a, ClipMap& mp) 
   }
 }
 
-// x rows [0, r1) of the chunk from its smoothed rows in LDS (s: row-major [*, 36], row 0 = the
-// chunk's first frame): normalize_data on the mapped row, rounded to float32 (k_normalize<true>)
+// x rows [0, r1) of the chunk (below row `end`: the clip's) from its smoothed rows in LDS (s:
+// row-major [*, 36], row 0 = the chunk's first frame): normalize_data on the mapped row, rounded
+// to float32 (k_normalize<true>)
 __device__ __forceinline__ void clip_write_x(const ClipInArgs& a, const double* s, int64_t c0, int r1,
-                                             const ClipMap& mp) {
+                                             const ClipMap& mp, int64_t end) {
 #pragma clang fp contract(off)
   const int total = r1 * a.U2;
   for (int idx = threadIdx.x; idx < total; idx += P3D_CLIP_THREADS) {
     const int i = idx / a.U2, u = idx - i * a.U2;
-    if (c0 + i >= a.N) break;
+    if (c0 + i >= end) break;
     const double* row = s + i * P3D_CLIP_COLS;
     const int kind = mp.kind[u], ca = mp.ca[u], cb = mp.cb[u];
     const double va = ca >= 0 ? row[ca] : 0.0, vb = cb >= 0 ? row[cb] : 0.0;
@@ -293,7 +295,7 @@ __global__ __launch_bounds__(P3D_CLIP_THREADS) void k_clip_in(ClipInArgs a) {
     const int64_t g = c0 * NC + idx;
     if (g < N * NC) a.xy_s[g] = sm[idx];
   }
-  clip_write_x(a, sm, c0, C, mp);
+  clip_write_x(a, sm, c0, C, mp, N);
 }
 
 // second launch, one workgroup per chunk k >= 1: the positions of the chunk's columns before
@@ -317,7 +319,7 @@ __global__ __launch_bounds__(P3D_CLIP_THREADS) void k_clip_in_carry(ClipInArgs a
   int mx = 0;
   for (int col = 0; col < NC; ++col) mx = max(mx, sfirst[col]);
   if (mx == 0) return;                             // (uniform: every column resolved in its chunk)
-  clip_lookback(a.w.mask, (int)k, NC, sfirst, sfound, smask);
+  clip_lookback(a.w.mask, (int)k, 0, NC, sfirst, sfound, smask);
   clip_load_map(a, mp);
   for (int idx = t; idx < mx * NC; idx += P3D_CLIP_THREADS) {
     const int i = idx / NC, col = idx - i * NC;
@@ -329,7 +331,7 @@ __global__ __launch_bounds__(P3D_CLIP_THREADS) void k_clip_in_carry(ClipInArgs a
     s[idx] = v;
   }
   __syncthreads();
-  clip_write_x(a, s, c0, mx, mp);
+  clip_write_x(a, s, c0, mx, mp, N);
 }
 
 // ---- k_clip_out -----------------------------------------------------------------------------
@@ -489,7 +491,7 @@ __global__ __launch_bounds__(P3D_CLIP_THREADS) void k_clip_out_carry(ClipOutArgs
   if (first <= 0) return;                          // (uniform)
   if (t == 0) sneed[0] = 1;
   __syncthreads();
-  clip_lookback(a.w.mask, (int)k, 1, sneed, sfound, smask);
+  clip_lookback(a.w.mask, (int)k, 0, 1, sneed, sfound, smask);
   const int j = sfound[0];
   const int64_t from = j >= 0 ? (int64_t)reinterpret_cast<const int32_t*>(a.w.last + (int64_t)j * NC)[0] : -1;
   for (int idx = t; idx < first * D; idx += P3D_CLIP_THREADS) {

@@ -15,6 +15,15 @@ sandbox normalises with).
 Not built (they need scipy / matplotlib and are not hot paths): ``--interpolation``
 (UnivariateSpline resampling, :240-291), the curve and pose plots, ``--write_gif``.  The driver
 refuses those flags.  ``--out_dir`` (build-specific) names the export directory.
+
+Build-specific, all in ONE ``p3d_clips_lift``: ``--clips_root DIR`` lifts every clip under DIR (each
+immediate subdirectory with frame files, exported to ``<out_dir>/<clip name>/``);
+``--vae_filter W.npz`` refines the lifted poses with the temporal VAE filter whose weights
+``3d_pose_vae_filter_kin.py`` saves (``--latent_dim`` / ``--enc_dim`` / ``--dec_dim`` as there),
+between the forward and the post-processing, every clip a fresh sequence; ``--filter_samples K``
+averages K posterior samples per frame; ``--export_unfiltered`` also writes
+``3d_data_unfiltered.json``, the poses without the filter.  Without these flags the driver does
+what it did before them.
 """
 from __future__ import annotations
 
@@ -35,7 +44,68 @@ def build_parser():
     p.add_argument("--out_dir", type=str, default="maya", help="directory of 3d_data.json / 2d_data.json")
     p.add_argument("--no_smooth", action="store_true", default=False,
                    help="skip the median smoothing (read_openpose_json(smooth=False))")
+    p.add_argument("--clips_root", type=str, default=None,
+                   help="lift every clip under this directory (one subdirectory of frame files each) in one call")
+    p.add_argument("--vae_filter", type=str, default=None,
+                   help="weights (.npz) of the temporal VAE filter, run between the forward and the post-processing")
+    p.add_argument("--filter_samples", type=int, default=None, help="average K posterior samples per frame (1 .. 64)")
+    p.add_argument("--export_unfiltered", action="store_true", default=False,
+                   help="also write 3d_data_unfiltered.json (needs --vae_filter)")
+    p.add_argument("--latent_dim", type=int, default=24, help="VAE latent dimension")
+    p.add_argument("--enc_dim", type=int, nargs="+", default=[40, 32], help="VAE encoder dimension")
+    p.add_argument("--dec_dim", type=int, nargs="+", default=[32, 40], help="VAE decoder dimension")
     return p
+
+
+def load_filter(flags, model):
+    """The temporal filter of --vae_filter on the lifter's device: its input width (seq_len * 48) is
+    the first encoder kernel's, read from the weights file."""
+    from top_vae_3d_pose import models
+    path = flags.vae_filter if flags.vae_filter.endswith(".npz") else flags.vae_filter + ".npz"
+    key = "enc_h_%d/kernel" % flags.enc_dim[0]
+    with np.load(path, allow_pickle=False) as z:
+        if key not in z.files:
+            raise SystemExit("--vae_filter %s has no %s: do --enc_dim / --dec_dim / --latent_dim match it?" % (path, key))
+        in_size = int(z[key].shape[0])
+    vae = models.VAE(in_size, latent_dim=flags.latent_dim, enc_dim=flags.enc_dim, dec_dim=flags.dec_dim,
+                     device=model.device.index)
+    vae.load_weights(path)
+    return vae
+
+
+def run_clips(flags):
+    """--clips_root / --vae_filter: one p3d_clips_lift over every clip."""
+    if flags.clips_root:
+        names, numbers, clips = of.read_clips(flags.clips_root)
+    else:
+        fn, xy = of.read_openpose_json(flags.pose_estimation_json)
+        names, numbers, clips = None, [fn], [xy]
+    smooth = not flags.no_smooth
+    of.check_clips(numbers, smooth, names)
+    d = p3.load_data(flags)
+    actions = data_utils.define_actions(flags.action)
+    with p3.Session() as sess:
+        model = p3.create_model(sess, actions, 128, flags)
+        lifter = of.ClipLifter(model, d["data_mean_2d"], d["data_std_2d"], d["dim_to_use_2d"], d["data_mean_3d"],
+                               d["data_std_3d"], d["dim_to_ignore_3d"], max_frames=sum(len(c) for c in clips),
+                               cache_on_fail=flags.cache_on_fail)
+        vae = load_filter(flags, model) if flags.vae_filter else None
+        logger.info("lifting %d clips, %d frames", len(clips), sum(len(c) for c in clips))
+        results = lifter.lift_clips(clips, smooth=smooth, vae=vae, samples=flags.filter_samples,
+                                    unfiltered=flags.export_unfiltered)
+        if vae is not None:
+            vae.close()
+        model.close()
+    if names is None:                                         # a single --pose_estimation_json clip
+        r = results[0]
+        paths = of.export_maya(flags.out_dir, numbers[0], r["poses"], r["xy_s"])
+        if flags.export_unfiltered:
+            paths += (of.export_unfiltered(flags.out_dir, numbers[0], r["poses_unfiltered"]),)
+    else:
+        paths = of.export_maya_clips(flags.out_dir, names, numbers, results, unfiltered=flags.export_unfiltered)
+    logger.info("exported maya json under %s", flags.out_dir)
+    logger.info("Done!")
+    return paths
 
 
 def run(flags):
@@ -45,6 +115,10 @@ def run(flags):
         raise SystemExit("--write_gif (matplotlib pose plots) is not part of this build")
     logging.basicConfig(level={0: logging.ERROR, 1: logging.WARNING, 2: logging.INFO,
                                3: logging.DEBUG}.get(flags.verbose, logging.INFO))
+    if (flags.filter_samples is not None or flags.export_unfiltered) and not flags.vae_filter:
+        raise SystemExit("--filter_samples and --export_unfiltered need --vae_filter")
+    if flags.clips_root or flags.vae_filter:
+        return run_clips(flags)
     logger.info("start reading json files")
     frame_numbers, xy = of.read_openpose_json(flags.pose_estimation_json)
     smooth = not flags.no_smooth

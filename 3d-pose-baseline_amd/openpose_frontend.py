@@ -17,6 +17,13 @@ in tiles of ``max_batch`` rows, the axis swap / flip / spine offset and ``--cach
 pinned rows in to pinned rows out.  ``read_openpose_json`` parses the frame files and
 ``export_maya`` writes ``3d_data.json`` / ``2d_data.json``.  The plots, ``--interpolation`` and
 ``--write_gif`` stay out of scope.
+
+``ClipLifter.lift_clips`` lifts a BATCH of clips in one ``p3d_clips_lift`` (every clip the bits of
+``lift_clip`` on it alone), optionally with the temporal VAE filter (``models.VAE``, the filter
+``3d_pose_vae_filter_kin.py`` trains) between the forward and the post-processing: the filter is
+a serial chain per clip and runs 16 clips per workgroup, so it pays over many clips at once.
+``read_clips`` / ``check_clips`` / ``export_maya_clips`` are the directory-of-clips forms of the
+reader, the check and the export.
 """
 from __future__ import annotations
 
@@ -232,6 +239,62 @@ def export_maya(out_dir, frame_numbers, poses, xy_s):
     return paths
 
 
+def read_clips(root):
+    """Every immediate subdirectory of `root` that holds frame files (*.json) is one clip, in sorted
+    order, each read by read_openpose_json -> (names [S], frame_numbers: S arrays, clips: S arrays
+    [n_s, 36]).  Subdirectories without frame files and plain files are ignored."""
+    names, numbers, clips = [], [], []
+    for name in sorted(os.listdir(root)):
+        d = os.path.join(root, name)
+        if not os.path.isdir(d) or not any(f.endswith(".json") for f in os.listdir(d)):
+            continue
+        fn, xy = read_openpose_json(d)
+        names.append(name)
+        numbers.append(fn)
+        clips.append(xy)
+    if not names:
+        raise ValueError("no clip directories with .json frame files in %s" % root)
+    return names, numbers, clips
+
+
+def check_clips(frame_numbers, smooth=True, names=None):
+    """check_clip on every clip; the error names the clip."""
+    for s, fn in enumerate(frame_numbers):
+        try:
+            check_clip(fn, smooth)
+        except ValueError as e:
+            raise ValueError("clip %s: %s" % (names[s] if names is not None else s, e)) from None
+
+
+def export_maya_clips(out_dir, names, frame_numbers, results, unfiltered=False):
+    """export_maya of every clip of a lift_clips result into <out_dir>/<clip name>/; with
+    unfiltered=True also ``3d_data_unfiltered.json`` (the lift without the filter) beside them.
+    Returns one tuple of paths per clip."""
+    if not len(names) == len(frame_numbers) == len(results):
+        raise ValueError("expected one name, one array of frame numbers and one result per clip")
+    paths = []
+    for name, fn, r in zip(names, frame_numbers, results):
+        d = os.path.join(out_dir, name)
+        p = export_maya(d, fn, r["poses"], r["xy_s"])
+        if unfiltered:
+            p += (export_unfiltered(d, fn, r["poses_unfiltered"]),)
+        paths.append(p)
+    return paths
+
+
+def export_unfiltered(out_dir, frame_numbers, poses):
+    """``3d_data_unfiltered.json``: the layout of ``3d_data.json`` for the poses before the filter."""
+    poses = np.asarray(poses, np.float64)
+    if poses.ndim != 2 or poses.shape[1] != 96 or len(frame_numbers) != poses.shape[0]:
+        raise ValueError("expected poses [N, 96] and N frame numbers")
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, "3d_data_unfiltered.json")
+    with open(path, "w") as f:
+        json.dump({int(frame): {j: {"translate": poses[n, 3 * j:3 * j + 3].tolist()} for j in range(32)}
+                   for n, frame in enumerate(frame_numbers)}, f)
+    return path
+
+
 class ClipLifter:
     """Lift whole OpenPose clips of up to `max_frames` frames with a float32 LinearModel: pinned
     rows in, ONE p3d_clip_lift (smoothing, mapping, forward tiles, post-processing), pinned rows
@@ -272,6 +335,10 @@ class ClipLifter:
             self.work_bytes = int(_p3d.lib().p3d_clip_lift_workspace(n, model.input_size, model.output_size))
             self.work = torch.empty((self.work_bytes + 256,), dtype=torch.uint8, device=dev)
         self.work_ptr = (self.work.data_ptr() + 255) // 256 * 256
+        # the batched call's offsets, workspace and optional outputs (set_offsets, _clips_buffers)
+        self._off, self._clips, self.hoff, self.doff = None, None, None, None
+        self.cwork, self.cwork_ptr, self.cwork_bytes = None, 0, 0
+        self.hout_u, self.hsrc_u, self.dout_u, self.dsrc_u, self.hvar, self.dvar = (None,) * 6
 
     def lift_device(self, n, smooth=True):
         """p3d_clip_lift of the first n rows of self.din into self.dxy / dout / dsrc (current stream)."""
@@ -282,13 +349,175 @@ class ClipLifter:
             p(self.m3), p(self.s3), p(self.u3), self.u3.numel(), 96, int(self.cache_on_fail), p(self.dxy),
             p(self.dout), p(self.dsrc), self.work_ptr, self.work_bytes, self.model.stream()), "p3d_clip_lift")
 
-    def network_rows(self, n):
+    def network_rows(self, n=None):
         """View of the network's normalised outputs [n, output_size] float32 that the last
-        lift of n frames left in the workspace (behind the scan's summaries and the input rows)."""
+        lift of n frames left in the workspace (behind the scan's summaries and the input rows);
+        n=None: the rows of the last lift_clips / lift_clips_device, all clips one after another."""
         import _p3d
         a256 = lambda b: (b + 255) // 256 * 256   # noqa: E731
+        if n is None:
+            return self._clips_rows(0)
         off = int(_p3d.lib().p3d_clip_workspace(n)) + a256(n * self.model.input_size * 4)
         return _p3d.device_view(self.work_ptr + off, (n, self.model.output_size), self.model.device.index)
+
+    # ------------------------------------------------------------------ a batch of clips
+    def _clips_rows(self, area):
+        """View of area 0 (the network's rows) or 1 (the filter's) of the batched workspace."""
+        import _p3d
+        if self._clips is None:
+            raise ValueError("no batched lift has run yet")
+        S, N, filtered = self._clips
+        if area == 1 and not filtered:
+            raise ValueError("the last batched lift ran without a filter")
+        a256 = lambda b: (b + 255) // 256 * 256   # noqa: E731
+        off = (int(_p3d.lib().p3d_clips_workspace(N, S)) + a256(N * self.model.input_size * 4)
+               + area * a256(N * self.model.output_size * 4))
+        return _p3d.device_view(self.cwork_ptr + off, (N, self.model.output_size), self.model.device.index)
+
+    def refined_rows(self):
+        """View of the filter's refined rows [N, output_size] float32 of the last batched lift."""
+        return self._clips_rows(1)
+
+    def set_offsets(self, offsets):
+        """Check the clip offsets [S + 1] (start at 0, no empty clip, end <= max_frames) and put them
+        where lift_clips_device reads them: a host copy for the library's checks and grids, and the
+        device copy the kernels read (uploaded on the current stream).  Returns (S, N)."""
+        torch = self.torch
+        off = np.asarray(offsets)
+        if off.ndim != 1 or off.shape[0] < 2 or not np.issubdtype(off.dtype, np.integer):
+            raise ValueError("clip offsets: expected an integer vector [S + 1], got %s %s" % (off.dtype, off.shape))
+        off = off.astype(np.int64)
+        if off[0] != 0 or (np.diff(off) <= 0).any() or off[-1] > self.max_frames:
+            raise ValueError("clip offsets must start at 0, every clip must have a frame, and at most "
+                             "max_frames = %d frames in all" % self.max_frames)
+        S = off.shape[0] - 1
+        if self.hoff is None or self.hoff.shape[0] < S + 1:
+            with torch.cuda.device(self.model.device):
+                self.hoff = torch.empty((S + 1,), dtype=torch.int64, pin_memory=True)
+                self.doff = torch.empty((S + 1,), dtype=torch.int64, device=self.model.device)
+        self.hoff.numpy()[:S + 1] = off
+        with torch.cuda.device(self.model.device):
+            self.doff[:S + 1].copy_(self.hoff[:S + 1], non_blocking=True)
+        self._off = off
+        return S, int(off[-1])
+
+    def _clips_buffers(self, S, filtered, unfiltered, variance):
+        """The batched call's workspace and optional outputs, grown on demand (a captured graph
+        holds the addresses: size them with one eager call of the same kind before capturing)."""
+        import _p3d
+        torch, dev, n = self.torch, self.model.device, self.max_frames
+        need = int(_p3d.lib().p3d_clips_lift_workspace(n, min(S, n), self.model.input_size, self.model.output_size,
+                                                       int(filtered)))
+        with torch.cuda.device(dev):
+            if self.cwork is None or need > self.cwork_bytes:
+                self.cwork = torch.empty((need + 256,), dtype=torch.uint8, device=dev)
+                self.cwork_ptr = (self.cwork.data_ptr() + 255) // 256 * 256
+                self.cwork_bytes = need
+            if unfiltered and self.dout_u is None:
+                self.hout_u = torch.empty((n, 96), dtype=torch.float64, pin_memory=True)
+                self.hsrc_u = torch.empty((n,), dtype=torch.int32, pin_memory=True)
+                self.dout_u = torch.empty((n, 96), dtype=torch.float64, device=dev)
+                self.dsrc_u = torch.empty((n,), dtype=torch.int32, device=dev)
+            if variance and self.dvar is None:
+                self.hvar = torch.empty((n, self.model.output_size), dtype=torch.float32, pin_memory=True)
+                self.dvar = torch.empty((n, self.model.output_size), dtype=torch.float32, device=dev)
+
+    def lift_clips_device(self, smooth=True, vae=None, samples=None, eps=None, ctr=0, eps_row0=0, unfiltered=False):
+        """ONE p3d_clips_lift of the rows self.din[:N] under the offsets of the last set_offsets, into
+        self.dxy / dout / dsrc (and dout_u / dsrc_u, dvar), on the current stream; capturable.  vae:
+        a models.VAE sequence filter run between the forward and the post-processing; samples=K:
+        the mean of K draws; eps: a device tensor [N, latent] ([K, N, latent]) or None for the
+        library's stream at (ctr, eps_row0 + row)."""
+        import _p3d
+        if self._off is None:
+            raise ValueError("set_offsets first")
+        S, N = self._off.shape[0] - 1, int(self._off[-1])
+        K = 0
+        if vae is None:
+            if samples is not None or eps is not None or unfiltered:
+                raise ValueError("samples, eps and unfiltered need a filter (vae=...)")
+        else:
+            vae._seq_len()                                   # (ValueError: bones, wide, not a sequence filter)
+            if vae.human_3d_size != self.model.output_size:
+                raise ValueError("the filter refines %d values per frame, the lifter predicts %d"
+                                 % (vae.human_3d_size, self.model.output_size))
+            if samples is not None:
+                K = vae._samples(samples, "lift_clips")
+            if eps is not None and (tuple(eps.shape) != ((K, N, vae.latent_dim) if K else (N, vae.latent_dim))
+                                    or eps.dtype != self.torch.float32 or not eps.is_cuda or not eps.is_contiguous()):
+                raise ValueError("eps: expected a contiguous float32 device tensor %s"
+                                 % (((K, N, vae.latent_dim) if K else (N, vae.latent_dim)),))
+        self._clips_buffers(S, vae is not None, unfiltered, K > 0)
+        p = _p3d.ptr
+        _p3d.check(_p3d.lib().p3d_clips_lift(
+            self.model._h, None if vae is None else vae._h, K, p(eps), int(ctr), int(eps_row0),
+            p(self.din), self._off.ctypes.data, p(self.doff), S, N, int(bool(smooth)),
+            p(self.m2), p(self.s2), p(self.u2), self.u2.numel(), p(self.m3), p(self.s3), p(self.u3), self.u3.numel(), 96,
+            int(self.cache_on_fail), p(self.dxy), p(self.dout), p(self.dsrc),
+            p(self.dout_u) if unfiltered else None, p(self.dsrc_u) if unfiltered else None,
+            p(self.dvar) if K else None, self.cwork_ptr, self.cwork_bytes, self.model.stream()), "p3d_clips_lift")
+        self._clips = (S, N, vae is not None)
+
+    def lift_clips(self, clips, smooth=True, vae=None, samples=None, eps=None, ctr=None, unfiltered=False):
+        """A list of clips, each [n_s, 36] raw keypoints in position order (sum n_s <= max_frames), in
+        ONE p3d_clips_lift: every clip is smoothed, lifted and post-processed as lift_clip does it
+        alone, bit for bit.  vae: a models.VAE sequence filter (in = seq_len * out) that refines the
+        network's rows before the post-processing, every clip a fresh sequence; samples=K: the mean of
+        K draws; eps: [N, latent] ([K, N, latent]) rows over the concatenated clips, or None for the
+        library's stream at counter ctr (None: a fresh one, as filter_sequences).  Returns one dict
+        per clip: 'poses' [n_s, 96], 'xy_s' [n_s, 36], 'src' [n_s] (positions inside the clip, -1
+        zeros), with unfiltered=True 'poses_unfiltered' / 'src_unfiltered' (the lift without the
+        filter) and with samples 'ref_var' [n_s, out] float32 (the draws' variance)."""
+        rows = [np.asarray(c, np.float64) for c in clips]
+        if not rows:
+            raise ValueError("expected at least one clip")
+        for r in rows:
+            if r.ndim != 2 or r.shape[1] != 36 or r.shape[0] < 1:
+                raise ValueError("expected clips of [n >= 1, 36] keypoint rows, got %s" % (r.shape,))
+            if smooth and 2 <= r.shape[0] <= 8:
+                raise ValueError("need more frames, min 9 frames for smoothing")
+        off = np.concatenate([[0], np.cumsum([r.shape[0] for r in rows])]).astype(np.int64)
+        N = int(off[-1])
+        if N > self.max_frames:
+            raise ValueError("%d frames in all, max_frames is %d" % (N, self.max_frames))
+        torch, K = self.torch, None
+        if vae is not None:
+            vae._seq_len()
+            K = None if samples is None else vae._samples(samples, "lift_clips")
+            if eps is not None:
+                eps = vae._eps_k(eps, K, N) if K else vae._dev(eps, vae.latent_dim, "eps")
+                if eps.shape[-2] != N:
+                    raise ValueError("eps: expected %d rows, got %d" % (N, eps.shape[-2]))
+            if ctr is None:
+                ctr = vae._calls + 1
+                vae._calls += K or 1
+        np.concatenate(rows, out=self.hin.numpy()[:N])
+        with torch.cuda.device(self.model.device):
+            self.set_offsets(off)
+            self.din[:N].copy_(self.hin[:N], non_blocking=True)
+            self.lift_clips_device(smooth, vae, samples, eps, ctr or 0, 0, unfiltered)
+            pairs = [(self.hxy, self.dxy), (self.hout, self.dout), (self.hsrc, self.dsrc)]
+            if unfiltered:
+                pairs += [(self.hout_u, self.dout_u), (self.hsrc_u, self.dsrc_u)]
+            if K:
+                pairs.append((self.hvar, self.dvar))
+            for h, d in pairs:
+                h[:N].copy_(d[:N], non_blocking=True)
+            torch.cuda.current_stream(self.model.device).synchronize()
+        self.model.check_errors()
+        out = []
+        for s in range(len(rows)):
+            a, b = int(off[s]), int(off[s + 1])
+            local = lambda t: np.where(t[a:b] >= 0, t[a:b] - a, -1).astype(np.int32)   # noqa: E731
+            d = {"poses": self.hout.numpy()[a:b].copy(), "xy_s": self.hxy.numpy()[a:b].copy(),
+                 "src": local(self.hsrc.numpy())}
+            if unfiltered:
+                d["poses_unfiltered"] = self.hout_u.numpy()[a:b].copy()
+                d["src_unfiltered"] = local(self.hsrc_u.numpy())
+            if K:
+                d["ref_var"] = self.hvar.numpy()[a:b].copy()
+            out.append(d)
+        return out
 
     def lift_clip(self, xy, smooth=True):
         """xy [N <= max_frames, 36] raw keypoints in position order -> (poses [N, 96] float64 mm,

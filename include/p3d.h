@@ -499,6 +499,58 @@ int p3d_clip_lift(p3d_model* m, const double* xy, int64_t N, int32_t smooth, con
                   const int32_t* use3, int32_t U3, int32_t D3, int32_t cache_on_fail, double* xy_s, double* poses,
                   int32_t* src, void* work, int64_t work_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * A BATCH of S clips stored one after another: rows [N, 36] and clip offsets [S + 1] (clip s is
+ * rows off[s] .. off[s + 1] - 1).  The same kernels' segmented forms: every
+ * position-dependent rule -- the four-frame windows of the first and last four positions, the
+ * never-flagged position 0, the hold's and the held pose's look-back -- uses the position inside
+ * its clip, and no window or carry reads a neighbouring clip.  Every clip's rows carry the bits of
+ * the single-clip call on that clip alone; a one-frame clip passes through unsmoothed.
+ *   clip_off_host: host int64 [S + 1], read at the call to validate and to size the grids (no copy,
+ *     no device round trip: the calls stay asynchronous and capturable);
+ *   clip_off_dev: the same values in device memory, read by the kernels (and by the filter as its
+ *     seq_off), clamped into [0, N]: a mismatch gives wrong rows, never an access outside the buffers.
+ * 1 <= S <= N <= 2^20, every clip at least one frame.  P3D_ERR_ARG without touching the GPU: a null
+ * argument; offsets that do not start at 0, decrease or do not end at N; an empty clip; a clip of
+ * 2-8 frames with smooth != 0 ("min 9 frames"); a short or misaligned workspace (8 bytes;
+ * p3d_clips_lift: 256); and what the single-clip calls refuse.  src holds row indices into the
+ * batch (-1: zeros: the clip has no good frame before).
+ * ------------------------------------------------------------------------------------- */
+int64_t p3d_clips_workspace(int64_t N, int64_t S);
+int p3d_clips_prepare(const double* xy, const int64_t* clip_off_host, const int64_t* clip_off_dev, int64_t S, int64_t N,
+                      int32_t smooth, const double* mean2, const double* std2, const int32_t* use2, int32_t U2,
+                      float* x, double* xy_s, void* work, int64_t work_bytes, void* stream);
+int p3d_clips_finish(const float* y, const int64_t* clip_off_host, const int64_t* clip_off_dev, int64_t S, int64_t N,
+                     const double* xy_s, const double* mean3, const double* std3, const int32_t* use3, int32_t U3,
+                     int32_t D3, int32_t cache_on_fail, double* poses, int32_t* src, void* work, int64_t work_bytes,
+                     void* stream);
+
+/* p3d_clip_lift over the batch, with the temporal VAE filter (p3d_vae_seq_filter; K >= 1:
+ * p3d_vae_seq_filter_mc) between the forward and the post-processing: prepare; the eval forward in
+ * tiles of max_batch rows that START AGAIN AT EVERY CLIP'S FIRST FRAME (the lifter picks its
+ * kernels by the batch size, so its bits depend on the tiling: with this rule clip s carries the
+ * bits of p3d_clip_lift on clip s alone; the price is a launch-bound forward on batches of very
+ * short clips); with v != NULL the filter over the clips as its sequences (seq_off = clip_off_dev,
+ * fresh state, eps [N, latent] / [K, N, latent] or NULL with ctr and eps_row0 as there) into a ref
+ * [N, U3] area of the workspace; finish on ref; and with poses_unfiltered != NULL a second finish
+ * on the network's own rows, its cache_on_fail judged on its own poses.  xy_s does not depend on
+ * the filter.  ref_var [N, U3] float32 (or NULL) receives the K samples' variance.
+ * P3D_ERR_ARG as above and: D3 != 96; dimension sets that do not match the model; a bf16 model;
+ * with a filter: v not a sequence filter with out == U3 and in == seq_len * U3, a bones filter, K
+ * outside 0 .. 64 (0: one draw through p3d_vae_seq_filter), ref_var with K == 0; without one:
+ * ref_var or the unfiltered outputs asked for.  `work`: p3d_clips_lift_workspace bytes, 256-byte
+ * aligned: the batch's summaries | x [N, U2] | y [N, U3] | ref [N, U3] (with_filter), each area
+ * 256-byte aligned. */
+int64_t p3d_clips_lift_workspace(int64_t N, int64_t S, int32_t U2, int32_t U3, int32_t with_filter);
+struct p3d_vae;   /* the VAE pose filter's handle (below) */
+int p3d_clips_lift(p3d_model* m, struct p3d_vae* v /* or NULL */, int32_t K, const float* eps, uint64_t ctr, int64_t eps_row0,
+                   const double* xy, const int64_t* clip_off_host, const int64_t* clip_off_dev, int64_t S, int64_t N,
+                   int32_t smooth, const double* mean2, const double* std2, const int32_t* use2, int32_t U2,
+                   const double* mean3, const double* std3, const int32_t* use3, int32_t U3, int32_t D3,
+                   int32_t cache_on_fail, double* xy_s, double* poses, int32_t* src,
+                   double* poses_unfiltered /* or NULL */, int32_t* src_unfiltered /* or NULL */,
+                   float* ref_var /* or NULL */, void* work, int64_t work_bytes, void* stream);
+
 /* np.mean / np.std (population) over axis 0 of x [F, D], D <= 256 -- the statistics of
  * src/data_utils.py:210-211 (normalization_stats).  Deterministic two-level column sums;
  * `work` must hold p3d_moments_workspace(F, D) bytes of device memory. */
