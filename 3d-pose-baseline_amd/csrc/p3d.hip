@@ -22,6 +22,7 @@
 #include "p3d_sample.h"
 #include "p3d_clip.h"
 #include "p3d_clips.h"
+#include "p3d_live.h"
 #include "p3d_serve.h"
 #include "p3d_serve6.h"
 #include "p3d_serve_plan.h"
@@ -2643,5 +2644,6 @@ extern "C" uint32_t p3d_crc32c(const void* data, int64_t n, uint32_t crc) {
 // The VAE pose filter, its noise and its bones (include/p3d.h; kernels in p3d_vae*.h, p3d_bones.h)
 #include "p3d_vae_host.h"
 #include "p3d_clips_host.h"
+#include "p3d_live_host.h"
 
 #include "p3d_dp.h"

@@ -180,6 +180,20 @@ __device__ __forceinline__ void clip_load_map(const ClipInArgs& a, ClipMap& mp) 
   }
 }
 
+// Used dimension u of the model's input row from one smoothed row (36 values): the mapped H3.6M
+// value, normalize_data, rounded to float32 (k_normalize<true>); a dimension outside the row: NaN
+__device__ __forceinline__ float clip_x_value(const double* row, const ClipMap& mp, int u) {
+#pragma clang fp contract(off)
+  const int kind = mp.kind[u], ca = mp.ca[u], cb = mp.cb[u];
+  const double va = ca >= 0 ? row[ca] : 0.0, vb = cb >= 0 ? row[cb] : 0.0;
+  double e = va;
+  if (kind >= 1) e = (va + vb) / 2;
+  if (kind == 2) e = 2 * vb - e;
+  float out = __builtin_nanf("");
+  if (kind >= 0) out = (float)((e - mp.mean[u]) / mp.stdv[u]);
+  return out;
+}
+
 // x rows [0, r1) of the chunk (below row `end`: the clip's) from its smoothed rows in LDS (s:
 // row-major [*, 36], row 0 = the chunk's first frame): normalize_data on the mapped row, rounded
 // to float32 (k_normalize<true>)
@@ -190,15 +204,7 @@ __device__ __forceinline__ void clip_write_x(const ClipInArgs& a, const double* 
   for (int idx = threadIdx.x; idx < total; idx += P3D_CLIP_THREADS) {
     const int i = idx / a.U2, u = idx - i * a.U2;
     if (c0 + i >= end) break;
-    const double* row = s + i * P3D_CLIP_COLS;
-    const int kind = mp.kind[u], ca = mp.ca[u], cb = mp.cb[u];
-    const double va = ca >= 0 ? row[ca] : 0.0, vb = cb >= 0 ? row[cb] : 0.0;
-    double e = va;
-    if (kind >= 1) e = (va + vb) / 2;
-    if (kind == 2) e = 2 * vb - e;
-    float out = __builtin_nanf("");
-    if (kind >= 0) out = (float)((e - mp.mean[u]) / mp.stdv[u]);
-    a.x[(c0 + i) * a.U2 + u] = out;
+    a.x[(c0 + i) * a.U2 + u] = clip_x_value(s + i * P3D_CLIP_COLS, mp, u);
   }
 }
 
@@ -358,6 +364,67 @@ __device__ __forceinline__ double clip_unnorm(const float* sy, int U3, const int
   return (double)v * sstd[d] + smean[d];
 }
 
+// One frame judged by 8 lanes x 4 joints (q = the lane's number among the 8; every lane of the
+// wave must call it: shuffles): _max / _min over the swapped z (strict compares: a NaN never
+// wins), then the frame's minimum over its 96 exported values (np.min: NaN if any is NaN).
+// Frame i of the rows sy [*, U3] with the spine offsets sox[i] / soz[i]; in: the frame exists.
+// good: the frame shows its own pose (--cache_on_fail: its minimum is not below -1000).
+__device__ __forceinline__ void clip_frame_judge(const float* sy, int U3, const int* pos, const double* smean,
+                                                 const double* sstd, int i, bool in, int q, const double* sox,
+                                                 const double* soz, int cache_on_fail, double& mx_out,
+                                                 double& mn_out, int& good) {
+#pragma clang fp contract(off)
+  double zs[4], mx = 0.0, mn = 10000.0;
+#pragma unroll
+  for (int jj = 0; jj < 4; ++jj) {
+    const int j = q * 4 + jj;
+    zs[jj] = in ? clip_unnorm(sy, U3, pos, smean, sstd, i, 3 * j + 1) : 0.0;   // z' = the reference's y
+    if (zs[jj] > mx) mx = zs[jj];
+    if (zs[jj] < mn) mn = zs[jj];
+  }
+#pragma unroll
+  for (int d = 1; d < 8; d <<= 1) {
+    const double omx = __shfl_xor(mx, d, 64), omn = __shfl_xor(mn, d, 64);
+    if (omx > mx) mx = omx;
+    if (omn < mn) mn = omn;
+  }
+  double lo = __builtin_inf();
+  int nan = 0;
+  if (in) {
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      const int j = q * 4 + jj;
+      const double ex = clip_unnorm(sy, U3, pos, smean, sstd, i, 3 * j) + sox[i];
+      const double ey = clip_unnorm(sy, U3, pos, smean, sstd, i, 3 * j + 2);
+      const double ez = ((mx - zs[jj]) + mn) + soz[i];
+      nan |= (ex != ex) || (ey != ey) || (ez != ez);
+      if (ex < lo) lo = ex;
+      if (ey < lo) lo = ey;
+      if (ez < lo) lo = ez;
+    }
+  }
+#pragma unroll
+  for (int d = 1; d < 8; d <<= 1) {
+    const double olo = __shfl_xor(lo, d, 64);
+    nan |= __shfl_xor(nan, d, 64);
+    if (olo < lo) lo = olo;
+  }
+  mx_out = mx; mn_out = mn;
+  good = !(cache_on_fail && !nan && lo < -1000.0);
+}
+
+// exported value d (0 .. 95) of frame sl: x + the spine offset, the swapped y, the flipped z
+// (smx / smn: the frame's _max / _min)
+__device__ __forceinline__ double clip_export_value(const float* sy, int U3, const int* pos, const double* smean,
+                                                    const double* sstd, int sl, int d, const double* smx,
+                                                    const double* smn, const double* sox, const double* soz) {
+#pragma clang fp contract(off)
+  const int j = d / 3, c = d - 3 * j;
+  if (c == 0) return clip_unnorm(sy, U3, pos, smean, sstd, sl, d) + sox[sl];
+  if (c == 1) return clip_unnorm(sy, U3, pos, smean, sstd, sl, d + 1);
+  return ((smx[sl] - clip_unnorm(sy, U3, pos, smean, sstd, sl, d - 1)) + smn[sl]) + soz[sl];
+}
+
 __global__ __launch_bounds__(P3D_CLIP_THREADS) void k_clip_out(ClipOutArgs a) {
 #pragma clang fp contract(off)
   constexpr int C = P3D_CLIP_CHUNK, D = P3D_CLIP_D3, NC = P3D_CLIP_COLS;
@@ -399,44 +466,12 @@ __global__ __launch_bounds__(P3D_CLIP_THREADS) void k_clip_out(ClipOutArgs a) {
   for (int i = t >> 3; i < C; i += P3D_CLIP_THREADS / 8) {   // (every lane runs every trip: shuffles)
     const int q = t & 7;
     const bool in = i < nf;
-    double zs[4], mx = 0.0, mn = 10000.0;
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-      const int j = q * 4 + jj;
-      zs[jj] = in ? clip_unnorm(sy, U3, pos, smean, sstd, i, 3 * j + 1) : 0.0;   // z' = the reference's y
-      if (zs[jj] > mx) mx = zs[jj];
-      if (zs[jj] < mn) mn = zs[jj];
-    }
-#pragma unroll
-    for (int d = 1; d < 8; d <<= 1) {
-      const double omx = __shfl_xor(mx, d, 64), omn = __shfl_xor(mn, d, 64);
-      if (omx > mx) mx = omx;
-      if (omn < mn) mn = omn;
-    }
-    double lo = __builtin_inf();
-    int nan = 0;
-    if (in) {
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) {
-        const int j = q * 4 + jj;
-        const double ex = clip_unnorm(sy, U3, pos, smean, sstd, i, 3 * j) + sox[i];
-        const double ey = clip_unnorm(sy, U3, pos, smean, sstd, i, 3 * j + 2);
-        const double ez = ((mx - zs[jj]) + mn) + soz[i];
-        nan |= (ex != ex) || (ey != ey) || (ez != ez);
-        if (ex < lo) lo = ex;
-        if (ey < lo) lo = ey;
-        if (ez < lo) lo = ez;
-      }
-    }
-#pragma unroll
-    for (int d = 1; d < 8; d <<= 1) {
-      const double olo = __shfl_xor(lo, d, 64);
-      nan |= __shfl_xor(nan, d, 64);
-      if (olo < lo) lo = olo;
-    }
+    double mx, mn;
+    int good;
+    clip_frame_judge(sy, U3, pos, smean, sstd, i, in, q, sox, soz, a.cache_on_fail, mx, mn, good);
     if (q == 0 && in) {
       smx[i] = mx; smn[i] = mn;
-      sgood[i] = !(a.cache_on_fail && !nan && lo < -1000.0);
+      sgood[i] = good;
     }
   }
   __syncthreads();
@@ -464,10 +499,7 @@ __global__ __launch_bounds__(P3D_CLIP_THREADS) void k_clip_out(ClipOutArgs a) {
     if (sl < 0 && k > 0) continue;
     double v = 0.0;
     if (sl >= 0) {
-      const int j = d / 3, c = d - 3 * j;
-      if (c == 0) v = clip_unnorm(sy, U3, pos, smean, sstd, sl, d) + sox[sl];
-      else if (c == 1) v = clip_unnorm(sy, U3, pos, smean, sstd, sl, d + 1);
-      else v = ((smx[sl] - clip_unnorm(sy, U3, pos, smean, sstd, sl, d - 1)) + smn[sl]) + soz[sl];
+      v = clip_export_value(sy, U3, pos, smean, sstd, sl, d, smx, smn, sox, soz);
     }
     a.poses[c0 * D + idx] = v;
   }

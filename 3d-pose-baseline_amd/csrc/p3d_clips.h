@@ -269,44 +269,12 @@ __global__ __launch_bounds__(P3D_CLIP_THREADS) void k_clips_out(ClipOutArgs a, C
   for (int i = t >> 3; i < C; i += P3D_CLIP_THREADS / 8) {   // (every lane runs every trip: shuffles)
     const int q = t & 7;
     const bool in = i < nf;
-    double zs[4], mx = 0.0, mn = 10000.0;
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-      const int j = q * 4 + jj;
-      zs[jj] = in ? clip_unnorm(sy, U3, pos, smean, sstd, i, 3 * j + 1) : 0.0;   // z' = the reference's y
-      if (zs[jj] > mx) mx = zs[jj];
-      if (zs[jj] < mn) mn = zs[jj];
-    }
-#pragma unroll
-    for (int d = 1; d < 8; d <<= 1) {
-      const double omx = __shfl_xor(mx, d, 64), omn = __shfl_xor(mn, d, 64);
-      if (omx > mx) mx = omx;
-      if (omn < mn) mn = omn;
-    }
-    double lo = __builtin_inf();
-    int nan = 0;
-    if (in) {
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) {
-        const int j = q * 4 + jj;
-        const double ex = clip_unnorm(sy, U3, pos, smean, sstd, i, 3 * j) + sox[i];
-        const double ey = clip_unnorm(sy, U3, pos, smean, sstd, i, 3 * j + 2);
-        const double ez = ((mx - zs[jj]) + mn) + soz[i];
-        nan |= (ex != ex) || (ey != ey) || (ez != ez);
-        if (ex < lo) lo = ex;
-        if (ey < lo) lo = ey;
-        if (ez < lo) lo = ez;
-      }
-    }
-#pragma unroll
-    for (int d = 1; d < 8; d <<= 1) {
-      const double olo = __shfl_xor(lo, d, 64);
-      nan |= __shfl_xor(nan, d, 64);
-      if (olo < lo) lo = olo;
-    }
+    double mx, mn;
+    int good;
+    clip_frame_judge(sy, U3, pos, smean, sstd, i, in, q, sox, soz, a.cache_on_fail, mx, mn, good);
     if (q == 0 && in) {
       smx[i] = mx; smn[i] = mn;
-      sgood[i] = !(a.cache_on_fail && !nan && lo < -1000.0);
+      sgood[i] = good;
     }
   }
   __syncthreads();
@@ -334,10 +302,7 @@ __global__ __launch_bounds__(P3D_CLIP_THREADS) void k_clips_out(ClipOutArgs a, C
     if (sl < 0 && !head) continue;
     double v = 0.0;
     if (sl >= 0) {
-      const int j = d / 3, c = d - 3 * j;
-      if (c == 0) v = clip_unnorm(sy, U3, pos, smean, sstd, sl, d) + sox[sl];
-      else if (c == 1) v = clip_unnorm(sy, U3, pos, smean, sstd, sl, d + 1);
-      else v = ((smx[sl] - clip_unnorm(sy, U3, pos, smean, sstd, sl, d - 1)) + smn[sl]) + soz[sl];
+      v = clip_export_value(sy, U3, pos, smean, sstd, sl, d, smx, smn, sox, soz);
     }
     a.poses[c0 * D + idx] = v;
   }

@@ -24,9 +24,15 @@ pinned rows in to pinned rows out.  ``read_openpose_json`` parses the frame file
 a serial chain per clip and runs 16 clips per workgroup, so it pays over many clips at once.
 ``read_clips`` / ``check_clips`` / ``export_maya_clips`` are the directory-of-clips forms of the
 reader, the check and the export.
+
+``LiveLifter`` lifts LIVE streams frame by frame (src/openpose_3dpose_sandbox_realtime.py; DESIGN.md
+8d): S slots with carried state on the device, one ``p3d_live_push`` per tick, and for every stream
+the rows of its lifetime are those of the clip path on the stream's whole frame list -- at a fixed
+delay of four frames with smoothing (the median looks ahead), none without.
 """
 from __future__ import annotations
 
+import ctypes
 import json
 import os
 import re
@@ -184,6 +190,17 @@ def parse_keypoints(data):
     return xy
 
 
+def read_frame_file(path):
+    """One frame file -> the 36 COCO-18 x/y values of its first person (key ``pose_keypoints_2d``
+    or ``pose_keypoints``)."""
+    with open(path) as f:
+        person = json.load(f)["people"][0]
+    xy = parse_keypoints(person["pose_keypoints_2d"] if "pose_keypoints_2d" in person else person["pose_keypoints"])
+    if len(xy) != 36:
+        raise ValueError("%s: expected 18 joints (36 values), got %d values" % (os.path.basename(path), len(xy)))
+    return xy
+
+
 def read_openpose_json(directory):
     """The frame files of `directory` (*.json, sorted by name) -> (frame_numbers [N] int64,
     xy [N, 36] float64), first person of each file, key ``pose_keypoints_2d`` or
@@ -196,13 +213,8 @@ def read_openpose_json(directory):
         digits = re.findall(r"(\d+)", name)
         if not digits:
             raise ValueError("no frame number in file name %s" % name)
-        with open(os.path.join(directory, name)) as f:
-            person = json.load(f)["people"][0]
-        xy = parse_keypoints(person["pose_keypoints_2d"] if "pose_keypoints_2d" in person else person["pose_keypoints"])
-        if len(xy) != 36:
-            raise ValueError("%s: expected 18 joints (36 values), got %d values" % (name, len(xy)))
         numbers.append(int(digits[-1]))
-        rows.append(xy)
+        rows.append(read_frame_file(os.path.join(directory, name)))
     return np.array(numbers, np.int64), np.array(rows, np.float64)
 
 
@@ -538,3 +550,174 @@ class ClipLifter:
             self.torch.cuda.current_stream(self.model.device).synchronize()
         self.model.check_errors()
         return self.hout.numpy()[:n].copy(), self.hxy.numpy()[:n].copy(), self.hsrc.numpy()[:n].copy()
+
+
+# --------------------------------------------------------------------------------------
+# live streams: src/openpose_3dpose_sandbox_realtime.py, with the clip path's semantics
+# --------------------------------------------------------------------------------------
+
+
+class LiveLifter:
+    """Lift up to `slots` live OpenPose streams frame by frame with a float32 LinearModel.  Every
+    tick (``push``) takes at most one raw frame (36 values) per open slot and returns the rows that
+    became final: with smoothing frame f once frame f + 4 has arrived (frames 0 .. 4 together at
+    the ninth frame, the last four at ``close``), without smoothing at once.  Concatenated over a
+    stream's lifetime the rows are ``poses`` / ``xy_s`` / ``src`` of ``ClipLifter.lift_clips`` on the
+    stream's whole frame list, bit for bit up to the forward's tiling (a tick's rows, in slot order,
+    in tiles of max_batch) and the filter's noise keys (the session's counter, row = rows emitted
+    before the tick).  This is the clip path's --cache_on_fail (a failing frame shows the last good
+    one from the stream's first frame on), not the realtime script's ``frame != 0`` variant.
+
+    vae: a models.VAE sequence filter between the forward and the post-processing, its buffer
+    carried per slot; samples=K: the mean of K draws (adds 'ref_var').  Pinned rows in and out, one
+    p3d_live_push per tick, then a wait on the model's completion word."""
+
+    def __init__(self, model, data_mean_2d, data_std_2d, dim_to_use_2d, data_mean_3d, data_std_3d,
+                 dim_to_ignore_3d, slots, cache_on_fail=True, smooth=True, vae=None, samples=None):
+        import torch
+        import _p3d
+        self.torch, self.model, self.S = torch, model, int(slots)
+        self.cache_on_fail, self.smooth, self.vae = bool(cache_on_fail), bool(smooth), vae
+        if model.bf16:
+            raise ValueError("LiveLifter: float32 models only")
+        if not 1 <= self.S <= 1 << 16:
+            raise ValueError("slots must be in [1, 2^16]")
+        D3 = int(np.asarray(data_mean_3d).shape[0])
+        use3 = np.setdiff1d(np.arange(D3), np.asarray(dim_to_ignore_3d, np.int64))
+        if D3 != 96 or np.asarray(data_mean_2d).shape[0] != 64:
+            raise ValueError("LiveLifter: needs the 64-wide 2D and 96-wide 3D statistics")
+        if len(use3) != model.output_size or len(dim_to_use_2d) != model.input_size:
+            raise ValueError("statistics do not match the model's %d inputs / %d outputs"
+                             % (model.input_size, model.output_size))
+        self.K = 0
+        if vae is None:
+            if samples is not None:
+                raise ValueError("samples needs a filter (vae=...)")
+        else:
+            vae._seq_len()                                   # (ValueError: bones, wide, not a sequence filter)
+            if vae.human_3d_size != model.output_size:
+                raise ValueError("the filter refines %d values per frame, the lifter predicts %d"
+                                 % (vae.human_3d_size, model.output_size))
+            if samples is not None:
+                self.K = vae._samples(samples, "LiveLifter")
+            self.ctr = vae._calls + 1                        # the session's noise counter(s), as a fresh
+            vae._calls += self.K or 1                        # filter_sequences call takes them
+        S, cap, dev, U3 = self.S, 5 * self.S, model.device, model.output_size
+        lib = _p3d.lib()
+        with torch.cuda.device(dev):
+            self.m2, self.s2 = dp.as_device(data_mean_2d), dp.as_device(data_std_2d)
+            self.m3, self.s3 = dp.as_device(data_mean_3d), dp.as_device(data_std_3d)
+            self.u2 = dp._dims(dim_to_use_2d, 64, "LiveLifter")
+            self.u3 = dp._dims(use3, D3, "LiveLifter")
+            pin = lambda shape, dt: torch.zeros(shape, dtype=dt, pin_memory=True)   # noqa: E731
+            i32, f64 = torch.int32, torch.float64
+            # the tick's table and the rows in and out: pinned, read and written by the kernels in place
+            self.hin, self.hpush = pin((S, 36), f64), pin((S,), i32)
+            self.hoff, self.hslot = pin((S + 1,), torch.int64), pin((cap,), i32)
+            self.hframe, self.hkind = pin((cap,), i32), pin((cap,), i32)
+            self.hxy, self.hout, self.hsrc = pin((cap, 36), f64), pin((cap, 96), f64), pin((cap,), i32)
+            self.hvar = pin((cap, U3), torch.float32) if self.K else None
+            self.state = torch.empty((int(lib.p3d_live_state_bytes(S, U3)),), dtype=torch.uint8, device=dev)
+            self.work_bytes = int(lib.p3d_live_push_workspace(S, model.input_size, U3, int(vae is not None)))
+            self.work = torch.empty((self.work_bytes + 256,), dtype=torch.uint8, device=dev)
+            self.fstate, self.fstarted = vae.new_seq_state(S) if vae is not None else (None, None)
+            _p3d.check(lib.p3d_live_reset(self.state.data_ptr(), S, -1, model.stream()), "p3d_live_reset")
+        self.work_ptr = (self.work.data_ptr() + 255) // 256 * 256
+        self.count = np.zeros(S, np.int32)                   # frames received per slot
+        self._push, self._close, self._short = np.zeros(S, np.uint8), np.zeros(S, np.uint8), np.zeros(S, np.int32)
+        self.is_open = np.zeros(S, bool)
+        self.emitted = 0                                     # rows emitted so far: the tick's eps_row0
+        self.hin_np = self.hin.numpy()
+
+    def latency(self):
+        """Pushes between a frame and its row: 4 with smoothing, 0 without."""
+        return 4 if self.smooth else 0
+
+    def open(self):
+        """A free slot, starting from nothing: no ring contents, no held joints, no last good pose, a
+        fresh filter buffer."""
+        import _p3d
+        free = np.flatnonzero(~self.is_open)
+        if not len(free):
+            raise ValueError("LiveLifter: all %d slots are open" % self.S)
+        slot = int(free[0])
+        with self.torch.cuda.device(self.model.device):
+            _p3d.check(_p3d.lib().p3d_live_reset(self.state.data_ptr(), self.S, slot, self.model.stream()),
+                       "p3d_live_reset")
+            if self.fstarted is not None:
+                self.fstarted[slot:slot + 1].zero_()
+        self.count[slot] = 0
+        self.is_open[slot] = True
+        return slot
+
+    def _slot(self, slot):
+        s = int(slot)
+        if s != slot or not 0 <= s < self.S or not self.is_open[s]:
+            raise ValueError("LiveLifter: slot %r is not open" % (slot,))
+        return s
+
+    def push(self, frames, close=()):
+        """One tick.  frames: {slot: the 36 raw keypoint values of the slot's next frame}; close:
+        slots whose stream ends (not among `frames`).  Returns {slot: dict(frames [n], poses [n, 96],
+        xy_s [n, 36], src [n] int32 stream-local, -1 zeros[, ref_var [n, out]])} for the slots with
+        rows that became final.  Closing a stream of 2 .. 8 frames under smoothing raises ValueError
+        naming the slot -- after freeing it, before anything of the tick has run: the other streams
+        are untouched and the tick can be pushed again without it."""
+        import _p3d
+        lib, model, S = _p3d.lib(), self.model, self.S
+        rows = {self._slot(s): np.asarray(xy, np.float64) for s, xy in frames.items()}
+        closing = sorted({self._slot(s) for s in close})
+        for s, xy in rows.items():
+            if xy.shape != (36,):
+                raise ValueError("LiveLifter: slot %d: expected 36 keypoint values, got %s" % (s, xy.shape))
+            if s in closing:
+                raise ValueError("LiveLifter: slot %d is pushed and closed in one tick" % s)
+        short = [s for s in closing if self.smooth and 2 <= self.count[s] <= 8]
+        if short:
+            n = int(self.count[short[0]])
+            self.count[short], self.is_open[short] = 0, False
+            raise ValueError("stream in slot %d: %d frames: need more frames, min 9 frames for smoothing" % (short[0], n))
+        self._push[:], self._close[:] = 0, 0
+        for s, xy in rows.items():
+            self._push[s] = 1
+            self.hin_np[s] = xy
+        self._close[closing] = 1
+        n_rows = ctypes.c_int64()
+        P = lambda t: t.data_ptr()   # noqa: E731
+        _p3d.check(lib.p3d_live_plan(S, int(self.smooth), self.count.ctypes.data, self._push.ctypes.data,
+                                     self._close.ctypes.data, P(self.hoff), P(self.hslot), P(self.hframe), P(self.hkind),
+                                     P(self.hpush), self._short.ctypes.data, ctypes.byref(n_rows)), "p3d_live_plan")
+        N, vae = int(n_rows.value), self.vae
+        with self.torch.cuda.device(model.device):
+            _p3d.check(lib.p3d_live_push(
+                model._h, None if vae is None else vae._h, self.K, self.ctr if vae is not None else 0, self.emitted,
+                P(self.state), _p3d.ptr(self.fstate), _p3d.ptr(self.fstarted), P(self.hin), P(self.hpush), P(self.hoff),
+                P(self.hframe), P(self.hkind), S, N, P(self.m2), P(self.s2), P(self.u2), self.u2.numel(), P(self.m3),
+                P(self.s3), P(self.u3), self.u3.numel(), 96, int(self.cache_on_fail), int(self.smooth), P(self.hxy),
+                P(self.hout), P(self.hsrc), _p3d.ptr(self.hvar), self.work_ptr, self.work_bytes, model.stream()),
+                "p3d_live_push")
+            # the tick's last launch signals the model's completion word: wait on that, not on the stream
+            _p3d.check(lib.p3d_host_signal(model._h, model.stream()), "p3d_host_signal")
+            model._hsig = (model._hsig + 1) & 0xffffffff
+            rc = lib.p3d_host_wait(model._h, model._hsig, model.stream())
+            if rc:
+                model.check_errors()
+                _p3d.check(rc, "p3d_host_wait")
+        self.emitted += N
+        self.is_open[closing] = False
+        off = self.hoff.numpy()
+        out = {}
+        for s in range(S):
+            a, b = int(off[s]), int(off[s + 1])
+            if b > a:
+                d = {"frames": self.hframe.numpy()[a:b].copy(), "poses": self.hout.numpy()[a:b].copy(),
+                     "xy_s": self.hxy.numpy()[a:b].copy(), "src": self.hsrc.numpy()[a:b].copy()}
+                if self.K:
+                    d["ref_var"] = self.hvar.numpy()[a:b].copy()
+                out[s] = d
+        return out
+
+    def close(self, slot):
+        """End the slot's stream: the rows that were still waiting for their window (the last four
+        frames; a one-frame stream's frame), as push returns them for one slot (None: no rows)."""
+        return self.push({}, close=(slot,)).get(int(slot))

@@ -551,6 +551,68 @@ int p3d_clips_lift(p3d_model* m, struct p3d_vae* v /* or NULL */, int32_t K, con
                    double* poses_unfiltered /* or NULL */, int32_t* src_unfiltered /* or NULL */,
                    float* ref_var /* or NULL */, void* work, int64_t work_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * S LIVE OpenPose streams lifted frame by frame with carried state (DESIGN.md 8d;
+ * src/openpose_3dpose_sandbox_realtime.py).  A session has S slots; each tick the caller pushes at
+ * most one raw frame (36 float64) to any subset of them and may close others; the tick returns the
+ * rows that became final.  For every stream the rows of its lifetime, concatenated, are xy_s / x /
+ * poses / src of the clip calls above on the stream's whole frame list, bit for bit (src: the
+ * stream-local frame, -1 with a zero pose while the stream has no good frame), up to the forward's
+ * tiling (a tick's rows, in slot order, are forwarded in tiles of max_batch rows) and the filter's
+ * noise keys (ctr, eps_row0 of the tick).  With smoothing a frame is final four pushes after its
+ * own (the median looks three frames ahead, and the last four frames of a stream take another
+ * window), at close for the last four; without, at once.
+ *
+ * p3d_live_plan is that rule, host only: count [S] (frames received, updated in place), push / close
+ * [S] (non-zero: the slot gets a frame / is closed; never both) -> row_off [S + 1], row_slot /
+ * row_frame / row_kind [<= 5 S] (kind 0 the frame itself, 1 head window f .. f+3, 2 middle f-3 ..
+ * f+3, 3 tail f-3 .. f), push_frame [S] (the pushed frame's number, -1), is_short [S] (closed with
+ * 2 .. 8 frames under smoothing: the stream is refused as a clip of that length is) and *n_rows.
+ *
+ * The tick's table -- xy_in [S, 36] (row s: the frame pushed to slot s), push_frame, row_off,
+ * row_frame, row_kind -- is PINNED HOST memory that the host checks at the call and the kernels read
+ * in place (no upload: the calls stay asynchronous); it must stay unchanged until the tick has
+ * run.  The device clamps every offset into [0, N] and masks every ring index.  `state`:
+ * p3d_live_state_bytes(S, U3) bytes of device memory, 8-byte aligned, reset by p3d_live_reset
+ * (slot < 0: all slots) before a slot's first frame.  1 <= S <= 65536, 0 <= N <= 5 S.
+ * P3D_ERR_ARG without touching the GPU: a null argument, S or N out of range, a row_off that does
+ * not start at 0, decreases, gives a slot more than 5 rows or does not end at N, a negative frame,
+ * a kind outside 0 .. 3 (or non-zero without smoothing), a misaligned state, U2 / U3 / D3 as at the
+ * clip calls, and at p3d_live_push what p3d_clips_lift refuses of the model, the filter, K and the
+ * workspace (p3d_live_push_workspace bytes, 256-byte aligned).
+ * ------------------------------------------------------------------------------------- */
+int p3d_live_plan(int64_t S, int32_t smooth, int32_t* count, const uint8_t* push, const uint8_t* close,
+                  int64_t* row_off, int32_t* row_slot, int32_t* row_frame, int32_t* row_kind, int32_t* push_frame,
+                  int32_t* is_short, int64_t* n_rows);
+int64_t p3d_live_state_bytes(int64_t S, int32_t U3);
+int p3d_live_reset(void* state, int64_t S, int64_t slot_or_minus1, void* stream);
+/* k_live_in: the pushed frames into the slots' rings; per row the window median, the hold from the
+ * slot's last smoothed row (never at frame 0), xy_s [N, 36] and x [N, U2] float32. */
+int p3d_live_prepare(const double* xy_in, const int32_t* push_frame, const int64_t* row_off, const int32_t* row_frame,
+                     const int32_t* row_kind, int64_t S, int64_t N, int32_t smooth, const double* mean2,
+                     const double* std2, const int32_t* use2, int32_t U2, void* state, float* x, double* xy_s,
+                     void* stream);
+/* k_live_out: per row of y [N, U3] p3d_clip_finish's arithmetic from that row's xy_s; with
+ * cache_on_fail a failing row shows the slot's last good pose and its frame (zeros and -1 where
+ * there is none) and a good row becomes it.  src may be NULL. */
+int p3d_live_finish(const float* y, const int64_t* row_off, const int32_t* row_frame, int64_t S, int64_t N,
+                    const double* xy_s, const double* mean3, const double* std3, const int32_t* use3, int32_t U3,
+                    int32_t D3, int32_t cache_on_fail, void* state, double* poses, int32_t* src, void* stream);
+/* One tick on `stream`: prepare; the eval forward of the tick's rows in tiles of max_batch; with
+ * v != NULL p3d_vae_seq_filter (K >= 1: p3d_vae_seq_filter_mc) over the slots as its sequences
+ * (seq_off = row_off, slots without rows empty) on the carried filter_state / filter_started
+ * ([S, (seq_len - 1) * U3] float32, [S] int32, as at p3d_vae_seq_filter; a reopened slot needs
+ * filter_started[slot] = 0) with the library's noise at (ctr, eps_row0 + row); finish on the refined
+ * rows.  ref_var [N, U3] float32 or NULL (needs K >= 1).  N == 0: the rings only. */
+int64_t p3d_live_push_workspace(int64_t S, int32_t U2, int32_t U3, int32_t with_filter);
+int p3d_live_push(p3d_model* m, struct p3d_vae* v /* or NULL */, int32_t K, uint64_t ctr, int64_t eps_row0,
+                  void* state, float* filter_state, int32_t* filter_started, const double* xy_in,
+                  const int32_t* push_frame, const int64_t* row_off, const int32_t* row_frame, const int32_t* row_kind,
+                  int64_t S, int64_t N, const double* mean2, const double* std2, const int32_t* use2, int32_t U2,
+                  const double* mean3, const double* std3, const int32_t* use3, int32_t U3, int32_t D3,
+                  int32_t cache_on_fail, int32_t smooth, double* xy_s, double* poses, int32_t* src,
+                  float* ref_var /* or NULL */, void* work, int64_t work_bytes, void* stream);
+
 /* np.mean / np.std (population) over axis 0 of x [F, D], D <= 256 -- the statistics of
  * src/data_utils.py:210-211 (normalization_stats).  Deterministic two-level column sums;
  * `work` must hold p3d_moments_workspace(F, D) bytes of device memory. */
