@@ -65,19 +65,19 @@ int rccl_ready() {
 // flat [begin, end) of gradient bucket k (layers lowest[k] .. the previous bucket's lowest - 1)
 void bucket_range(const p3d_model* m, int k, int64_t& fb, int64_t& fe) {
   const int nl = (int)m->layers.size();
-  const int hi = k == 0 ? nl - 1 : m->bucket_lo[k - 1] - 1, lo = m->bucket_lo[k];
+  const int hi = k == 0 ? nl - 1 : m->train.bucket_lo[k - 1] - 1, lo = m->train.bucket_lo[k];
   fb = m->layers[lo].w;
   fe = hi + 1 < nl ? m->layers[hi + 1].w : m->n_flat;
 }
 
 // the N > 1 form: several ranks, or one forced into it (P3D_DP_FORCE_MULTI)
-bool dp_multi(const p3d_model* m) { return m->comm->nranks > 1 || m->dp_force_multi; }
+bool dp_multi(const p3d_model* m) { return m->dp.comm->nranks > 1 || m->knobs.dp_force_multi; }
 
 int dp_allreduce(p3d_model* m, float* buf, int64_t n, hipStream_t st) {
   // in place; the identity on one rank (nothing enqueued), the replica mean otherwise (ncclAvg: on a
   // forced 1-rank group the mean of one replica, still the identity)
   const ncclRedOp_t op = dp_multi(m) ? ncclAvg : ncclSum;
-  const ncclResult_t r = g_rccl.all_reduce(buf, buf, (size_t)n, ncclFloat32, op, m->comm->nc, st);
+  const ncclResult_t r = g_rccl.all_reduce(buf, buf, (size_t)n, ncclFloat32, op, m->dp.comm->nc, st);
   return r == ncclSuccess ? P3D_OK : rccl_fail("p3d_train_step_dp: ncclAllReduce", r);
 }
 
@@ -159,9 +159,9 @@ extern "C" int p3d_comm_allreduce(p3d_comm* c, void* buf, int64_t n, int32_t dty
 
 extern "C" int p3d_dp_attach(p3d_model* m, p3d_comm* c) {
   if (!m) return fail(P3D_ERR_ARG, "p3d_dp_attach: null model");
-  m->comm = c;
-  if (c && !m->cst) HIP_TRY(hipStreamCreateWithFlags(&m->cst, hipStreamNonBlocking));
-  if (c && !m->cjoin) HIP_TRY(hipEventCreateWithFlags(&m->cjoin, hipEventDisableTiming));
+  m->dp.comm = c;
+  if (c && !m->dp.cst) HIP_TRY(hipStreamCreateWithFlags(&m->dp.cst, hipStreamNonBlocking));
+  if (c && !m->dp.cjoin) HIP_TRY(hipEventCreateWithFlags(&m->dp.cjoin, hipEventDisableTiming));
   return P3D_OK;
 }
 
@@ -174,17 +174,17 @@ extern "C" int p3d_train_step_dp(p3d_model* m, const float* x, const float* t, i
                                  float keep_prob, uint64_t seed, int64_t row_offset, float lr0, float decay_steps,
                                  float decay_rate, float* loss_dev, void* stream) {
   if (!m) return fail(P3D_ERR_ARG, "p3d_train_step_dp: null model");
-  if (!m->comm) return fail(P3D_ERR_STATE, "p3d_train_step_dp: no communicator (p3d_dp_attach)");
+  if (!m->dp.comm) return fail(P3D_ERR_STATE, "p3d_train_step_dp: no communicator (p3d_dp_attach)");
   if (int rc = rccl_ready()) return rc;
   hipStream_t st = (hipStream_t)stream;
   int rc = p3d_train_fwd_bwd_lr(m, x, t, B, y, keep_prob, seed, row_offset, lr0, decay_steps, decay_rate,
                                 loss_dev, stream);
   if (rc) return rc;
-  const int nb = (int)m->gev.size();
+  const int nb = (int)m->train.gev.size();
   // the backward ran the bucketed form (one weight-gradient launch + event per bucket) exactly when
   // p3d_backward's condition held: buckets planned, no max-norm (its clip gradient needs every G)
-  const bool bucketed = nb > 0 && !m->cfg.max_norm && m->wgrad_multi && (int)m->bucket_lo.size() == nb &&
-                        (int)m->bat.size() == nb;
+  const bool bucketed = nb > 0 && !m->cfg.max_norm && m->knobs.wgrad_multi && (int)m->train.bucket_lo.size() == nb &&
+                        (int)m->train.bat.size() == nb;
   if (!bucketed) {
     if (dp_multi(m) && (rc = dp_allreduce(m, m->flat[1], m->n_flat, st))) return rc;
     return p3d_adam_apply(m, stream);
@@ -194,38 +194,38 @@ extern "C" int p3d_train_step_dp(p3d_model* m, const float* x, const float* t, i
     // it, so no comm-stream branch either (a forked branch in a captured graph puts its edges on
     // another hardware queue and slowed every launch of the step by 0.4-0.7 us, r04 A/B): each
     // bucket's optimizer follows on the compute stream
-    if (m->dp_adam == 0) return p3d_adam_apply(m, stream);
+    if (m->knobs.dp_adam == 0) return p3d_adam_apply(m, stream);
     for (int k = 0; k < nb; ++k)
       if ((rc = p3d_adam_apply_bucket(m, k, stream))) return rc;
     return P3D_OK;
   }
-  if ((int)m->rev.size() != nb) {
-    for (hipEvent_t e : m->rev) HIP_TRY(hipEventDestroy(e));
-    m->rev.assign((size_t)nb, nullptr);
-    for (hipEvent_t& e : m->rev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  if ((int)m->dp.rev.size() != nb) {
+    for (hipEvent_t e : m->dp.rev) HIP_TRY(hipEventDestroy(e));
+    m->dp.rev.assign((size_t)nb, nullptr);
+    for (hipEvent_t& e : m->dp.rev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   }
   for (int k = 0; k < nb; ++k) {
     int64_t fb, fe;
     bucket_range(m, k, fb, fe);
-    HIP_TRY(hipStreamWaitEvent(m->cst, m->gev[k], 0));
-    if ((rc = dp_allreduce(m, m->flat[1] + fb, fe - fb, m->cst))) return rc;
-    if (m->dp_adam == 2) {                         // optimizer on the comm stream behind its bucket
-      if ((rc = p3d_adam_apply_bucket(m, k, m->cst))) return rc;
+    HIP_TRY(hipStreamWaitEvent(m->dp.cst, m->train.gev[k], 0));
+    if ((rc = dp_allreduce(m, m->flat[1] + fb, fe - fb, m->dp.cst))) return rc;
+    if (m->knobs.dp_adam == 2) {                         // optimizer on the comm stream behind its bucket
+      if ((rc = p3d_adam_apply_bucket(m, k, m->dp.cst))) return rc;
     } else {
-      HIP_TRY(hipEventRecord(m->rev[k], m->cst));
+      HIP_TRY(hipEventRecord(m->dp.rev[k], m->dp.cst));
     }
   }
-  if (m->dp_adam == 2) {
-    HIP_TRY(hipEventRecord(m->cjoin, m->cst));
-    HIP_TRY(hipStreamWaitEvent(st, m->cjoin, 0));
+  if (m->knobs.dp_adam == 2) {
+    HIP_TRY(hipEventRecord(m->dp.cjoin, m->dp.cst));
+    HIP_TRY(hipStreamWaitEvent(st, m->dp.cjoin, 0));
     return P3D_OK;
   }
-  if (m->dp_adam == 0) {                           // one optimizer pass after the last bucket
-    for (int k = 0; k < nb; ++k) HIP_TRY(hipStreamWaitEvent(st, m->rev[k], 0));
+  if (m->knobs.dp_adam == 0) {                           // one optimizer pass after the last bucket
+    for (int k = 0; k < nb; ++k) HIP_TRY(hipStreamWaitEvent(st, m->dp.rev[k], 0));
     return p3d_adam_apply(m, stream);
   }
   for (int k = 0; k < nb; ++k) {                   // per bucket, on the compute stream
-    HIP_TRY(hipStreamWaitEvent(st, m->rev[k], 0));
+    HIP_TRY(hipStreamWaitEvent(st, m->dp.rev[k], 0));
     if ((rc = p3d_adam_apply_bucket(m, k, stream))) return rc;
   }
   return P3D_OK;

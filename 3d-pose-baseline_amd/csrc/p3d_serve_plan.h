@@ -1,7 +1,7 @@
 // p3d_serve_plan.h -- which serve kernel a p3d_serve / p3d_serve_mse launch runs: the list of the
 // built forms and the planner that picks one.  Host-only (no HIP header): the decision is a pure
 // function of (model shape, CU count, knobs, batch, with-loss), so it is tested without a GPU
-// (p3d_serve_plan, tests/test_serve_plan.py).  p3d.hip attaches the kernel pointers to the list.
+// (p3d_serve_plan, tests/test_serve_plan.py).  p3d_serve_host.h attaches the kernel pointers to the list.
 #pragma once
 #include <algorithm>
 #include <cstdint>

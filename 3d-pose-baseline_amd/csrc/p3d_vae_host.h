@@ -1,6 +1,6 @@
 // p3d_vae_host.h -- the VAE pose filter's host side (include/p3d.h): the handle, create / destroy,
 // the launches and every extern "C" entry point of the filter, its noise and its bones.  Host code;
-// included by p3d.hip behind fail(), LAUNCH_CHECK, HIP_TRY and aligned16.  What needs no device --
+// included by p3d.hip behind p3d_host.h (fail(), LAUNCH_CHECK, HIP_TRY, aligned16).  What needs no device --
 // shape checks, layouts, the kernel list -- is p3d_vae_layout.h; the kernels are in p3d_vae*.h and
 // p3d_bones.h.
 #pragma once

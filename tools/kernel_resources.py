@@ -8,6 +8,7 @@ spilling to scratch fails in the build container, not on the box) and for the AG
 DESIGN.md 6 asks for before any k_serve6 measurement.
 
     python tools/kernel_resources.py [libp3d.so] [--filter SUBSTRING]
+    python tools/kernel_resources.py --compare A.so B.so    # two builds, kernel by kernel; exit 1 if any differ
 """
 from __future__ import annotations
 
@@ -80,7 +81,54 @@ def kernel_isa(name_prefix, lib=LIB, arch="gfx950"):
     raise KeyError(name_prefix)
 
 
+def _code_listing(lib, arch="gfx950"):
+    """{mangled symbol: instruction lines} of `lib`'s `arch` code object, addresses, encodings and
+    branch-label numbers stripped (what is left of a kernel does not depend on where it was placed)."""
+    with tempfile.TemporaryDirectory() as d:
+        fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "co.o")
+        subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "--dump-section=.hip_fatbin=" + fat, lib, os.devnull],
+                       check=True, capture_output=True)
+        subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat,
+                        "--targets=hipv4-amdgcn-amd-amdhsa--" + arch, "--output=" + co], check=True, capture_output=True)
+        dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--symbolize-operands", co], check=True,
+                             capture_output=True, text=True).stdout.split("\n")
+    head = re.compile(r"^[0-9a-f]{16} <(\S+)>:$")
+    out, cur = {}, None
+    for line in dis:
+        m = head.match(line)
+        if m and not re.fullmatch(r"L\d+", m.group(1)):
+            cur = out.setdefault(m.group(1), [])
+        elif cur is not None and line.strip():
+            cur.append("<L>:" if m else re.sub(r"\bL\d+\b", "L", line.split("//")[0].strip()))
+    for lines in out.values():   # the alignment padding up to the next symbol (or the section's end)
+        while lines and lines[-1] in ("s_nop 0", "s_code_end", "..."):
+            lines.pop()
+    return out
+
+
+def compare(lib_a, lib_b, arch="gfx950"):
+    """Demangled names of the kernels that differ between two builds' `arch` code objects: present in
+    one only, any figure of kernel_resources() unequal, or the stripped disassembly unequal."""
+    ra, rb = kernel_resources(lib_a, arch), kernel_resources(lib_b, arch)
+    ca, cb = _code_listing(lib_a, arch), _code_listing(lib_b, arch)
+    differ = sorted(set(ra) ^ set(rb))
+    for name in sorted(set(ra) & set(rb)):
+        a, b = ra[name], rb[name]
+        if a != b or ca.get(a["mangled"]) is None or ca.get(a["mangled"]) != cb.get(b["mangled"]):
+            differ.append(name)
+    kernels = {r["mangled"] for r in list(ra.values()) + list(rb.values())}
+    differ += sorted(s for s in (set(ca) | set(cb)) - kernels if ca.get(s) != cb.get(s))   # device functions
+    return differ, len(set(ra) | set(rb))
+
+
 def main(argv):
+    if "--compare" in argv:
+        a, b = argv[argv.index("--compare") + 1:][:2]
+        differ, n = compare(a, b)
+        for name in differ:
+            print("differs:", name)
+        print("%d of %d kernels equal" % (n - len(differ), n))
+        sys.exit(1 if differ else 0)
     lib = next((a for a in argv if a.endswith(".so")), LIB)
     flt = argv[argv.index("--filter") + 1] if "--filter" in argv else ""
     res = kernel_resources(lib)
