@@ -59,6 +59,8 @@
 #include "p3d_data_host.h"
 // The VAE pose filter, its noise and its bones (include/p3d.h; kernels in p3d_vae*.h, p3d_bones.h)
 #include "p3d_vae_host.h"
+// One clip, a batch of clips, live streams: p3d_clip_host.h also holds the stage the three share
+#include "p3d_clip_host.h"
 #include "p3d_clips_host.h"
 #include "p3d_live_host.h"
 

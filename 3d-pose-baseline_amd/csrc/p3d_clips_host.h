@@ -1,11 +1,11 @@
 // p3d_clips_host.h -- the host side of a batch of OpenPose clips (include/p3d.h: p3d_clips_*):
 // S clips stored one after another through the segmented clip kernels (p3d_clips.h), the
 // eval forward tiled clip by clip, and between the forward and the post-processing the temporal
-// VAE filter over the clips as its sequences.  Included by p3d.hip behind p3d_vae_host.h.
+// VAE filter over the clips as its sequences.  Included by p3d.hip behind p3d_clip_host.h (the single
+// clip's helpers and the stage the lift calls share).
 //
 // workspace (bytes): chunk_base i32 [S + 1] (256-aligned) | the scan's summaries of p3d_clip_workspace
-// over the largest chunk total S clips of N frames can have.  p3d_clips_lift adds x [N, U2], y [N, U3]
-// and, with a filter, ref [N, U3] (float32, each 256-aligned).
+// over the largest chunk total S clips of N frames can have.  p3d_clips_lift adds LiftLayout's rows.
 #pragma once
 
 namespace {
@@ -63,11 +63,10 @@ int clips_index(const ClipsPlan& pl, int64_t N, hipStream_t st) {
   return P3D_OK;
 }
 
-int clips_prepare(const ClipsPlan& pl, const double* xy, int64_t N, int32_t smooth, const double* mean2,
-                  const double* std2, const int32_t* use2, int32_t U2, float* x, double* xy_s, hipStream_t st) {
-  ClipInArgs a{};
-  a.xy = xy; a.N = N; a.smooth = smooth ? 1 : 0;
-  a.mean2 = mean2; a.std2 = std2; a.use2 = use2; a.U2 = U2; a.x = x; a.xy_s = xy_s;
+int clips_prepare(const ClipsPlan& pl, const double* xy, int64_t N, int32_t smooth, const Stat2& s2, float* x,
+                  double* xy_s, hipStream_t st) {
+  ClipInArgs a = lift_in_args(s2, N, x, xy_s);
+  a.xy = xy; a.smooth = smooth ? 1 : 0;
   a.w = pl.w;
   k_clips_in<<<dim3(pl.nch), P3D_CLIP_THREADS, 0, st>>>(a, pl.g);
   LAUNCH_CHECK("k_clips_in");
@@ -78,14 +77,11 @@ int clips_prepare(const ClipsPlan& pl, const double* xy, int64_t N, int32_t smoo
   return P3D_OK;
 }
 
-int clips_finish(const ClipsPlan& pl, const float* y, int64_t N, const double* xy_s, const double* mean3,
-                 const double* std3, const int32_t* use3, int32_t U3, int32_t cache_on_fail, double* poses,
+int clips_finish(const ClipsPlan& pl, const float* y, int64_t N, const double* xy_s, const Stat3& s3, double* poses,
                  int32_t* src, hipStream_t st) {
-  ClipOutArgs a{};
-  a.y = y; a.N = N; a.xy_s = xy_s; a.mean3 = mean3; a.std3 = std3; a.use3 = use3; a.U3 = U3;
-  a.cache_on_fail = cache_on_fail ? 1 : 0; a.poses = poses; a.src = src;
+  ClipOutArgs a = lift_out_args(s3, y, N, xy_s, poses, src);
   a.w = pl.w;
-  const size_t lds = (size_t)P3D_CLIP_CHUNK * U3 * sizeof(float);
+  const size_t lds = (size_t)P3D_CLIP_CHUNK * s3.U * sizeof(float);
   k_clips_out<<<dim3(pl.nch), P3D_CLIP_THREADS, lds, st>>>(a, pl.g);
   LAUNCH_CHECK("k_clips_out");
   if (a.cache_on_fail && pl.multi) {   // the held pose across chunk boundaries inside a clip
@@ -113,7 +109,7 @@ extern "C" int p3d_clips_prepare(const double* xy, const int64_t* clip_off_host,
   if ((const double*)xy_s == xy) return fail(P3D_ERR_ARG, "p3d_clips_prepare: xy_s must not alias xy");
   hipStream_t st = (hipStream_t)stream;
   if (int rc = clips_index(pl, N, st)) return rc;
-  return clips_prepare(pl, xy, N, smooth, mean2, std2, use2, U2, x, xy_s, st);
+  return clips_prepare(pl, xy, N, smooth, {mean2, std2, use2, U2}, x, xy_s, st);
 }
 
 extern "C" int p3d_clips_finish(const float* y, const int64_t* clip_off_host, const int64_t* clip_off_dev, int64_t S,
@@ -127,17 +123,16 @@ extern "C" int p3d_clips_finish(const float* y, const int64_t* clip_off_host, co
   if (U3 < 1 || U3 > D3) return fail(P3D_ERR_ARG, "p3d_clips_finish: U3 must be in 1..96");
   hipStream_t st = (hipStream_t)stream;
   if (int rc = clips_index(pl, N, st)) return rc;
-  return clips_finish(pl, y, N, xy_s, mean3, std3, use3, U3, cache_on_fail, poses, src, st);
+  return clips_finish(pl, y, N, xy_s, {mean3, std3, use3, U3, cache_on_fail}, poses, src, st);
 }
 
 extern "C" int64_t p3d_clips_lift_workspace(int64_t N, int64_t S, int32_t U2, int32_t U3, int32_t with_filter) {
   if (N <= 0 || S <= 0 || S > N || U2 <= 0 || U3 <= 0) return 0;
-  const int64_t yb = align256(N * U3 * (int64_t)sizeof(float));
-  return p3d_clips_workspace(N, S) + align256(N * U2 * (int64_t)sizeof(float)) + yb + (with_filter ? yb : 0);
+  return LiftLayout(nullptr, p3d_clips_workspace(N, S), N, U2, U3, with_filter != 0).total;
 }
 
-// index, prepare, the eval forward in tiles of max_batch rows that start again at every clip's
-// first frame (clip s carries p3d_clip_lift's bits on clip s alone), the temporal filter over the
+// index, prepare, the forward tiles starting again at every clip's first frame (clip s carries
+// p3d_clip_lift's bits on clip s alone), the temporal filter over the
 // clips as its sequences (fresh state), finish on the refined rows and, where asked for, a second
 // finish on the network's own rows -- all on `stream`
 extern "C" int p3d_clips_lift(p3d_model* m, p3d_vae* v, int32_t K, const float* eps, uint64_t ctr, int64_t eps_row0,
@@ -151,10 +146,7 @@ extern "C" int p3d_clips_lift(p3d_model* m, p3d_vae* v, int32_t K, const float* 
   if (!m) return fail(P3D_ERR_ARG, "p3d_clips_lift: null model");
   if (!xy || !mean2 || !std2 || !use2 || !mean3 || !std3 || !use3 || !xy_s || !poses)
     return fail(P3D_ERR_ARG, "p3d_clips_lift: null argument");
-  const p3d_cfg& c = m->cfg;
-  if (c.dtype != P3D_DTYPE_F32) return fail(P3D_ERR_ARG, "p3d_clips_lift: float32 models only");
-  if (U2 != c.input_size || U3 != c.output_size)
-    return fail(P3D_ERR_ARG, "p3d_clips_lift: dimension sets do not match the model");
+  if (int rc = lift_check_model(what, m, U2, U3)) return rc;
   if (U2 < 1 || U2 > 64 || U3 < 1 || U3 > P3D_CLIP_D3) return fail(P3D_ERR_ARG, "p3d_clips_lift: U2 must be in 1..64, U3 in 1..96");
   if (D3 != P3D_CLIP_D3) return fail(P3D_ERR_ARG, "p3d_clips_lift: D3 must be 96 (32 joints)");
   if ((const double*)xy_s == xy) return fail(P3D_ERR_ARG, "p3d_clips_lift: xy_s must not alias xy");
@@ -162,10 +154,7 @@ extern "C" int p3d_clips_lift(p3d_model* m, p3d_vae* v, int32_t K, const float* 
     if (ref_var || poses_unfiltered || src_unfiltered)
       return fail(P3D_ERR_ARG, "p3d_clips_lift: ref_var and the unfiltered outputs need a filter");
   } else {
-    const VaePlan& p = v->plan;
-    if (p.shape.kind != P3D_VAE_KIND_ELBO) return fail(P3D_ERR_ARG, "p3d_clips_lift: a bones filter has no sequence form");
-    if (p.wide || p.desc.out != U3 || p.desc.in % p.desc.out != 0 || p.desc.in / p.desc.out > P3D_VAE_SEQ_MAX_LEN || !p.seq_lds)
-      return fail(P3D_ERR_ARG, "p3d_clips_lift: the filter must be a sequence filter with out == U3 and in == seq_len * U3");
+    if (int rc = lift_check_filter(what, v, U3)) return rc;
     if (K < 0 || K > P3D_VAE_MC_MAX_K)
       return fail(P3D_ERR_ARG, "p3d_clips_lift: K must be in 1 .. " + std::to_string(P3D_VAE_MC_MAX_K) + " (0: one draw)");
     if (K >= 1 && ctr == P3D_CTR_GLOBAL_STEP)
@@ -178,31 +167,19 @@ extern "C" int p3d_clips_lift(p3d_model* m, p3d_vae* v, int32_t K, const float* 
   }
   ClipsPlan pl;
   if (int rc = clips_check(what, clip_off_host, clip_off_dev, S, N, smooth, work, work_bytes, pl)) return rc;
-  if (work_bytes < p3d_clips_lift_workspace(N, S, U2, U3, v != nullptr))
-    return fail(P3D_ERR_ARG, "p3d_clips_lift: workspace too small");
+  const LiftLayout l(work, p3d_clips_workspace(N, S), N, U2, U3, v != nullptr);
+  if (work_bytes < l.total) return fail(P3D_ERR_ARG, "p3d_clips_lift: workspace too small");
   if ((uintptr_t)work & 255) return fail(P3D_ERR_ARG, "p3d_clips_lift: workspace must be 256-byte aligned");
-  const int64_t yb = align256(N * U3 * (int64_t)sizeof(float));
-  float* x = (float*)((char*)work + p3d_clips_workspace(N, S));
-  float* y = (float*)((char*)x + align256(N * U2 * (int64_t)sizeof(float)));
-  float* ref = (float*)((char*)y + yb);
+  const Stat3 s3{mean3, std3, use3, U3, cache_on_fail};
   hipStream_t st = (hipStream_t)stream;
-  int rc = clips_index(pl, N, st);
-  if (rc) return rc;
-  rc = clips_prepare(pl, xy, N, smooth, mean2, std2, use2, U2, x, xy_s, st);
-  if (rc) return rc;
+  if (int rc = clips_index(pl, N, st)) return rc;
+  if (int rc = clips_prepare(pl, xy, N, smooth, {mean2, std2, use2, U2}, l.x, xy_s, st)) return rc;
   for (int64_t s = 0; s < S; ++s)
-    for (int64_t r = clip_off_host[s]; r < clip_off_host[s + 1]; r += c.max_batch) {
-      const int64_t left = clip_off_host[s + 1] - r, B = left < c.max_batch ? left : (int64_t)c.max_batch;
-      rc = forward_impl(m, x + r * U2, B, y + r * U3, 0, 1.0f, 0, 0, 0, 0, stream, nullptr);
-      if (rc) return rc;
-    }
-  if (!v) return clips_finish(pl, y, N, xy_s, mean3, std3, use3, U3, cache_on_fail, poses, src, st);
-  rc = K >= 1 ? p3d_vae_seq_filter_mc(v, y, clip_off_dev, S, N, K, eps, ctr, eps_row0, nullptr, nullptr, nullptr, ref,
-                                      ref_var, nullptr, nullptr, stream)
-              : p3d_vae_seq_filter(v, y, clip_off_dev, S, N, eps, ctr, eps_row0, nullptr, nullptr, nullptr, ref, nullptr,
-                                   nullptr, stream);
-  if (rc) return rc;
-  rc = clips_finish(pl, ref, N, xy_s, mean3, std3, use3, U3, cache_on_fail, poses, src, st);
+    if (int rc = lift_forward(m, l.x, l.y, clip_off_host[s], clip_off_host[s + 1], stream)) return rc;
+  if (!v) return clips_finish(pl, l.y, N, xy_s, s3, poses, src, st);
+  if (int rc = lift_filter_run(v, K, l.y, clip_off_dev, S, N, eps, ctr, eps_row0, nullptr, nullptr, l.ref, ref_var, stream))
+    return rc;
+  const int rc = clips_finish(pl, l.ref, N, xy_s, s3, poses, src, st);
   if (rc || !poses_unfiltered) return rc;
-  return clips_finish(pl, y, N, xy_s, mean3, std3, use3, U3, cache_on_fail, poses_unfiltered, src_unfiltered, st);
+  return clips_finish(pl, l.y, N, xy_s, s3, poses_unfiltered, src_unfiltered, st);
 }

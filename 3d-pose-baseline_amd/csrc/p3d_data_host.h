@@ -1,9 +1,8 @@
 // p3d_data_host.h -- the entry points around the network (include/p3d.h): the MPJPE accumulation,
 // DLPack aliases, the empty launch, the H3.6M data pipeline (camera, normalise / unnormalise,
-// p3d_sample_world, moments), p3d_lift, the single-clip calls (p3d_clip_*) and CRC-32C.  Host
-// code (and the one-line k_empty); included by p3d.hip behind p3d_forward_host.h (forward_impl,
-// forward_gemv) and p3d_model.h; the kernels are in p3d_eval.h, p3d_data.h, p3d_sample.h and
-// p3d_clip.h.
+// p3d_sample_world, moments), p3d_lift and CRC-32C.  Host code (and the one-line k_empty);
+// included by p3d.hip behind p3d_forward_host.h (forward_impl, forward_gemv) and p3d_model.h; the
+// kernels are in p3d_eval.h, p3d_data.h and p3d_sample.h.  The clip calls: p3d_clip_host.h.
 #pragma once
 
 extern "C" int p3d_mpjpe_accum_ex(const float* pred_n, const float* gt_n, int32_t D, const double* mean96,
@@ -211,112 +210,6 @@ extern "C" int p3d_lift(p3d_model* m, const double* raw, int64_t B, int32_t D2, 
   r = forward_impl(m, m->gemv.lift_x, B, m->gemv.lift_y, 0, 1.0f, 0, 0, 0, 0, stream, nullptr);
   if (r) return r;
   return p3d_unnormalize(m->gemv.lift_y, P3D_DTYPE_F32, B, U3, mean3, std3, use3, D3, out, stream);
-}
-
-// ---- a whole OpenPose clip (p3d_clip.h; src/openpose_3dpose_sandbox.py:140-227, 317-417) ---------
-static int64_t align256(int64_t n) { return (n + 255) / 256 * 256; }
-
-static ClipWork clip_work(void* work, int64_t N) {
-  const int64_t nch = p3d_clip_chunks(N);
-  char* p = (char*)work;
-  ClipWork w;
-  w.mask = (unsigned long long*)p;
-  w.last = (double*)(p + nch * 8);
-  w.first = (int32_t*)(p + nch * 8 + nch * P3D_CLIP_COLS * 8);
-  return w;
-}
-
-extern "C" int32_t p3d_clip_chunk(void) { return P3D_CLIP_CHUNK; }
-
-extern "C" int64_t p3d_clip_workspace(int64_t N) {
-  if (N <= 0) return 0;
-  return align256(p3d_clip_chunks(N) * (8 + P3D_CLIP_COLS * (8 + 4)));
-}
-
-static int clip_check_n(const char* what, int64_t N, int32_t smooth, void* work, int64_t work_bytes) {
-  if (N < 1 || N > P3D_CLIP_MAX_N)
-    return fail(P3D_ERR_ARG, std::string(what) + ": N must be in 1.." + std::to_string(P3D_CLIP_MAX_N) + " frames");
-  if (smooth && N >= 2 && N <= 8)
-    return fail(P3D_ERR_ARG, std::string(what) + ": need more frames, min 9 frames for smoothing");
-  if (!work || ((uintptr_t)work & 7)) return fail(P3D_ERR_ARG, std::string(what) + ": null or misaligned workspace");
-  if (work_bytes < p3d_clip_workspace(N)) return fail(P3D_ERR_ARG, std::string(what) + ": workspace too small");
-  return P3D_OK;
-}
-
-extern "C" int p3d_clip_prepare(const double* xy, int64_t N, int32_t smooth, const double* mean2, const double* std2,
-                                const int32_t* use2, int32_t U2, float* x, double* xy_s, void* work,
-                                int64_t work_bytes, void* stream) {
-  if (!xy || !mean2 || !std2 || !use2 || !x || !xy_s) return fail(P3D_ERR_ARG, "p3d_clip_prepare: null argument");
-  if (int rc = clip_check_n("p3d_clip_prepare", N, smooth, work, work_bytes)) return rc;
-  if (U2 < 1 || U2 > 64) return fail(P3D_ERR_ARG, "p3d_clip_prepare: U2 must be in 1..64");
-  if ((const double*)xy_s == xy) return fail(P3D_ERR_ARG, "p3d_clip_prepare: xy_s must not alias xy");
-  ClipInArgs a{};
-  a.xy = xy; a.N = N; a.smooth = (smooth && N > 1) ? 1 : 0;   // (a single frame passes through, :140-143)
-  a.mean2 = mean2; a.std2 = std2; a.use2 = use2; a.U2 = U2; a.x = x; a.xy_s = xy_s;
-  a.w = clip_work(work, N);
-  const unsigned nch = (unsigned)p3d_clip_chunks(N);
-  hipStream_t st = (hipStream_t)stream;
-  k_clip_in<<<dim3(nch), P3D_CLIP_THREADS, 0, st>>>(a);
-  LAUNCH_CHECK("k_clip_in");
-  if (a.smooth && nch > 1) {   // the hold across chunk boundaries
-    k_clip_in_carry<<<dim3(nch - 1), P3D_CLIP_THREADS, 0, st>>>(a);
-    LAUNCH_CHECK("k_clip_in_carry");
-  }
-  return P3D_OK;
-}
-
-extern "C" int p3d_clip_finish(const float* y, int64_t N, const double* xy_s, const double* mean3, const double* std3,
-                               const int32_t* use3, int32_t U3, int32_t D3, int32_t cache_on_fail, double* poses,
-                               int32_t* src, void* work, int64_t work_bytes, void* stream) {
-  if (!y || !xy_s || !mean3 || !std3 || !use3 || !poses) return fail(P3D_ERR_ARG, "p3d_clip_finish: null argument");
-  if (int rc = clip_check_n("p3d_clip_finish", N, 0, work, work_bytes)) return rc;
-  if (D3 != P3D_CLIP_D3) return fail(P3D_ERR_ARG, "p3d_clip_finish: D3 must be 96 (32 joints)");
-  if (U3 < 1 || U3 > D3) return fail(P3D_ERR_ARG, "p3d_clip_finish: U3 must be in 1..96");
-  ClipOutArgs a{};
-  a.y = y; a.N = N; a.xy_s = xy_s; a.mean3 = mean3; a.std3 = std3; a.use3 = use3; a.U3 = U3;
-  a.cache_on_fail = cache_on_fail ? 1 : 0; a.poses = poses; a.src = src;
-  a.w = clip_work(work, N);
-  const unsigned nch = (unsigned)p3d_clip_chunks(N);
-  hipStream_t st = (hipStream_t)stream;
-  const size_t lds = (size_t)P3D_CLIP_CHUNK * U3 * sizeof(float);
-  k_clip_out<<<dim3(nch), P3D_CLIP_THREADS, lds, st>>>(a);
-  LAUNCH_CHECK("k_clip_out");
-  if (a.cache_on_fail && nch > 1) {   // the held pose across chunk boundaries
-    k_clip_out_carry<<<dim3(nch - 1), P3D_CLIP_THREADS, 0, st>>>(a);
-    LAUNCH_CHECK("k_clip_out_carry");
-  }
-  return P3D_OK;
-}
-
-extern "C" int64_t p3d_clip_lift_workspace(int64_t N, int32_t U2, int32_t U3) {
-  if (N <= 0 || U2 <= 0 || U3 <= 0) return 0;
-  return p3d_clip_workspace(N) + align256(N * U2 * (int64_t)sizeof(float)) + align256(N * U3 * (int64_t)sizeof(float));
-}
-
-// prepare, the eval forward in tiles of max_batch rows (the forward_impl of p3d_lift's three-step
-// form: every tile's rows carry p3d_lift's bits at that batch), finish -- all on `stream`
-extern "C" int p3d_clip_lift(p3d_model* m, const double* xy, int64_t N, int32_t smooth, const double* mean2,
-                             const double* std2, const int32_t* use2, int32_t U2, const double* mean3,
-                             const double* std3, const int32_t* use3, int32_t U3, int32_t D3, int32_t cache_on_fail,
-                             double* xy_s, double* poses, int32_t* src, void* work, int64_t work_bytes, void* stream) {
-  if (!m) return fail(P3D_ERR_ARG, "p3d_clip_lift: null model");
-  const p3d_cfg& c = m->cfg;
-  if (c.dtype != P3D_DTYPE_F32) return fail(P3D_ERR_ARG, "p3d_clip_lift: float32 models only");
-  if (U2 != c.input_size || U3 != c.output_size) return fail(P3D_ERR_ARG, "p3d_clip_lift: dimension sets do not match the model");
-  if (int rc = clip_check_n("p3d_clip_lift", N, smooth, work, work_bytes)) return rc;
-  if (work_bytes < p3d_clip_lift_workspace(N, U2, U3)) return fail(P3D_ERR_ARG, "p3d_clip_lift: workspace too small");
-  if ((uintptr_t)work & 255) return fail(P3D_ERR_ARG, "p3d_clip_lift: workspace must be 256-byte aligned");
-  const int64_t wb = p3d_clip_workspace(N);
-  float* x = (float*)((char*)work + wb);
-  float* y = (float*)((char*)x + align256(N * U2 * (int64_t)sizeof(float)));
-  int rc = p3d_clip_prepare(xy, N, smooth, mean2, std2, use2, U2, x, xy_s, work, wb, stream);
-  if (rc) return rc;
-  for (int64_t r = 0; r < N; r += c.max_batch) {
-    const int64_t B = N - r < c.max_batch ? N - r : (int64_t)c.max_batch;
-    rc = forward_impl(m, x + r * U2, B, y + r * U3, 0, 1.0f, 0, 0, 0, 0, stream, nullptr);
-    if (rc) return rc;
-  }
-  return p3d_clip_finish(y, N, xy_s, mean3, std3, use3, U3, D3, cache_on_fail, poses, src, work, wb, stream);
 }
 
 extern "C" int64_t p3d_moments_workspace(int64_t F, int32_t D) {

@@ -1,10 +1,9 @@
 // p3d_live_host.h -- the host side of S live OpenPose streams (include/p3d.h: p3d_live_*): the
 // tick planner's export, the per-slot state, the two kernels of p3d_live.h as calls of their own and
 // p3d_live_push, one tick from pushed frames to final poses.  Included by p3d.hip behind
-// p3d_clips_host.h.
+// p3d_clips_host.h; the stage it shares with the clip calls is in p3d_clip_host.h.
 //
-// p3d_live_push's workspace (bytes, cap = 5 S rows): x [cap, U2] | y [cap, U3] | ref [cap, U3]
-// (with a filter), float32, each 256-aligned.
+// p3d_live_push's workspace: LiftLayout's rows without a head, cap = 5 S rows.
 #pragma once
 
 namespace {
@@ -53,24 +52,21 @@ int live_prepare_check(const char* what, const double* xy_in, const int32_t* pus
 
 unsigned live_grid(int64_t S) { return (unsigned)((S + P3D_LIVE_WAVES - 1) / P3D_LIVE_WAVES); }
 
-int live_prepare(const LiveTick& t, const double* xy_in, const int32_t* push_frame, const double* mean2,
-                 const double* std2, const int32_t* use2, int32_t U2, void* state, float* x, double* xy_s,
-                 hipStream_t st) {
+int live_prepare(const LiveTick& t, const double* xy_in, const int32_t* push_frame, const Stat2& s2, void* state,
+                 float* x, double* xy_s, hipStream_t st) {
   LiveInArgs a{};
-  a.c.mean2 = mean2; a.c.std2 = std2; a.c.use2 = use2; a.c.U2 = U2; a.c.x = x; a.c.xy_s = xy_s; a.c.N = t.N;
+  a.c = lift_in_args(s2, t.N, x, xy_s);
   a.xy = xy_in; a.push_frame = push_frame; a.t = t; a.st = live_state(state, t.S);
   k_live_in<<<dim3(live_grid(t.S)), P3D_LIVE_WAVES * 64, 0, st>>>(a);
   LAUNCH_CHECK("k_live_in");
   return P3D_OK;
 }
 
-int live_finish(const LiveTick& t, const float* y, const double* xy_s, const double* mean3, const double* std3,
-                const int32_t* use3, int32_t U3, int32_t cache_on_fail, void* state, double* poses, int32_t* src,
-                hipStream_t st) {
+int live_finish(const LiveTick& t, const float* y, const double* xy_s, const Stat3& s3, void* state, double* poses,
+                int32_t* src, hipStream_t st) {
   if (t.N == 0) return P3D_OK;   // (no row: no state changes)
   LiveOutArgs a{};
-  a.c.y = y; a.c.N = t.N; a.c.xy_s = xy_s; a.c.mean3 = mean3; a.c.std3 = std3; a.c.use3 = use3; a.c.U3 = U3;
-  a.c.cache_on_fail = cache_on_fail ? 1 : 0; a.c.poses = poses; a.c.src = src;
+  a.c = lift_out_args(s3, y, t.N, xy_s, poses, src);
   a.t = t; a.st = live_state(state, t.S);
   k_live_out<<<dim3(live_grid(t.S)), P3D_LIVE_WAVES * 64, 0, st>>>(a);
   LAUNCH_CHECK("k_live_out");
@@ -127,7 +123,7 @@ extern "C" int p3d_live_prepare(const double* xy_in, const int32_t* push_frame, 
   if (int rc = live_check(what, row_off, row_frame, row_kind, S, N, state, t)) return rc;
   if (int rc = live_prepare_check(what, xy_in, push_frame, row_kind, S, N, smooth, U2)) return rc;
   if (N > 0 && (!x || !xy_s)) return fail(P3D_ERR_ARG, "p3d_live_prepare: null x or xy_s");
-  return live_prepare(t, xy_in, push_frame, mean2, std2, use2, U2, state, x, xy_s, (hipStream_t)stream);
+  return live_prepare(t, xy_in, push_frame, {mean2, std2, use2, U2}, state, x, xy_s, (hipStream_t)stream);
 }
 
 extern "C" int p3d_live_finish(const float* y, const int64_t* row_off, const int32_t* row_frame, int64_t S, int64_t N,
@@ -141,18 +137,17 @@ extern "C" int p3d_live_finish(const float* y, const int64_t* row_off, const int
   if (D3 != P3D_CLIP_D3) return fail(P3D_ERR_ARG, "p3d_live_finish: D3 must be 96 (32 joints)");
   if (U3 < 1 || U3 > D3) return fail(P3D_ERR_ARG, "p3d_live_finish: U3 must be in 1..96");
   if (N > 0 && (!y || !xy_s || !poses)) return fail(P3D_ERR_ARG, "p3d_live_finish: null y, xy_s or poses");
-  return live_finish(t, y, xy_s, mean3, std3, use3, U3, cache_on_fail, state, poses, src, (hipStream_t)stream);
+  return live_finish(t, y, xy_s, {mean3, std3, use3, U3, cache_on_fail}, state, poses, src, (hipStream_t)stream);
 }
 
 extern "C" int64_t p3d_live_push_workspace(int64_t S, int32_t U2, int32_t U3, int32_t with_filter) {
   if (S < 1 || S > P3D_LIVE_MAX_S || U2 <= 0 || U3 <= 0) return 0;
-  const int64_t yb = align256(live_cap(S) * U3 * (int64_t)sizeof(float));
-  return align256(live_cap(S) * U2 * (int64_t)sizeof(float)) + yb + (with_filter ? yb : 0);
+  return LiftLayout(nullptr, 0, live_cap(S), U2, U3, with_filter != 0).total;
 }
 
-// One tick on `stream`: prepare; the eval forward of the tick's rows, in slot order, in tiles of
-// max_batch rows; the temporal filter over the slots as its sequences (slots without rows are empty
-// sequences) on the carried state; finish on the refined rows.
+// One tick on `stream`: prepare; the forward tiles over the tick's rows in slot order; the temporal
+// filter over the slots as its sequences (slots without rows are empty sequences) on the carried
+// state; finish on the refined rows.
 extern "C" int p3d_live_push(p3d_model* m, p3d_vae* v, int32_t K, uint64_t ctr, int64_t eps_row0, void* state,
                              float* filter_state, int32_t* filter_started, const double* xy_in,
                              const int32_t* push_frame, const int64_t* row_off, const int32_t* row_frame,
@@ -174,16 +169,13 @@ extern "C" int p3d_live_push(p3d_model* m, p3d_vae* v, int32_t K, uint64_t ctr, 
   if (int rc = live_check(what, row_off, row_frame, row_kind, S, N, state, t)) return rc;
   if (int rc = live_prepare_check(what, xy_in, push_frame, row_kind, S, N, smooth, U2)) return rc;
   if (!work || ((uintptr_t)work & 255)) return fail(P3D_ERR_ARG, "p3d_live_push: null workspace, or not 256-byte aligned");
-  if (work_bytes < p3d_live_push_workspace(S, U2, U3, v != nullptr))
-    return fail(P3D_ERR_ARG, "p3d_live_push: workspace too small");
+  const LiftLayout l(work, 0, live_cap(S), U2, U3, v != nullptr);
+  if (work_bytes < l.total) return fail(P3D_ERR_ARG, "p3d_live_push: workspace too small");
   if (!v) {
     if (K || ref_var || filter_state || filter_started)
       return fail(P3D_ERR_ARG, "p3d_live_push: K, ref_var and the filter state need a filter");
   } else {
-    const VaePlan& p = v->plan;
-    if (p.shape.kind != P3D_VAE_KIND_ELBO) return fail(P3D_ERR_ARG, "p3d_live_push: a bones filter has no sequence form");
-    if (p.wide || p.desc.out != U3 || p.desc.in % p.desc.out != 0 || p.desc.in / p.desc.out > P3D_VAE_SEQ_MAX_LEN || !p.seq_lds)
-      return fail(P3D_ERR_ARG, "p3d_live_push: the filter must be a sequence filter with out == U3 and in == seq_len * U3");
+    if (int rc = lift_check_filter(what, v, U3)) return rc;
     if (ctr == P3D_CTR_GLOBAL_STEP)
       return fail(P3D_ERR_ARG, "p3d_live_push: ctr may not be P3D_CTR_GLOBAL_STEP (draw k uses the counter ctr + k)");
     if (ref_var && K < 1) return fail(P3D_ERR_ARG, "p3d_live_push: ref_var needs K >= 1");
@@ -192,27 +184,15 @@ extern "C" int p3d_live_push(p3d_model* m, p3d_vae* v, int32_t K, uint64_t ctr, 
       return fail(P3D_ERR_ARG, "p3d_live_push: filter_state and ref_var must be 16-byte aligned");
   }
   if (!m) return fail(P3D_ERR_ARG, "p3d_live_push: null model");
-  const p3d_cfg& c = m->cfg;
-  if (c.dtype != P3D_DTYPE_F32) return fail(P3D_ERR_ARG, "p3d_live_push: float32 models only");
-  if (U2 != c.input_size || U3 != c.output_size)
-    return fail(P3D_ERR_ARG, "p3d_live_push: dimension sets do not match the model");
-  const int64_t yb = align256(live_cap(S) * U3 * (int64_t)sizeof(float));
-  float* x = (float*)work;
-  float* y = (float*)((char*)x + align256(live_cap(S) * U2 * (int64_t)sizeof(float)));
-  float* ref = (float*)((char*)y + yb);
+  if (int rc = lift_check_model(what, m, U2, U3)) return rc;
+  const Stat3 s3{mean3, std3, use3, U3, cache_on_fail};
   hipStream_t st = (hipStream_t)stream;
-  int rc = live_prepare(t, xy_in, push_frame, mean2, std2, use2, U2, state, x, xy_s, st);
+  int rc = live_prepare(t, xy_in, push_frame, {mean2, std2, use2, U2}, state, l.x, xy_s, st);
   if (rc || N == 0) return rc;
-  for (int64_t r = 0; r < N; r += c.max_batch) {
-    const int64_t B = N - r < c.max_batch ? N - r : (int64_t)c.max_batch;
-    rc = forward_impl(m, x + r * U2, B, y + r * U3, 0, 1.0f, 0, 0, 0, 0, stream, nullptr);
-    if (rc) return rc;
-  }
-  if (!v) return live_finish(t, y, xy_s, mean3, std3, use3, U3, cache_on_fail, state, poses, src, st);
-  rc = K >= 1 ? p3d_vae_seq_filter_mc(v, y, row_off, S, N, K, nullptr, ctr, eps_row0, nullptr, filter_state,
-                                      filter_started, ref, ref_var, nullptr, nullptr, stream)
-              : p3d_vae_seq_filter(v, y, row_off, S, N, nullptr, ctr, eps_row0, nullptr, filter_state, filter_started,
-                                   ref, nullptr, nullptr, stream);
-  if (rc) return rc;
-  return live_finish(t, ref, xy_s, mean3, std3, use3, U3, cache_on_fail, state, poses, src, st);
+  if ((rc = lift_forward(m, l.x, l.y, 0, N, stream))) return rc;
+  if (!v) return live_finish(t, l.y, xy_s, s3, state, poses, src, st);
+  if ((rc = lift_filter_run(v, K, l.y, row_off, S, N, nullptr, ctr, eps_row0, filter_state, filter_started, l.ref,
+                            ref_var, stream)))
+    return rc;
+  return live_finish(t, l.ref, xy_s, s3, state, poses, src, st);
 }

@@ -266,6 +266,50 @@ int vae_add_noise(const float* src, int64_t rows, int32_t d, const int64_t* star
   return P3D_OK;
 }
 
+// why no K-sample call takes a bones filter
+const char* const kVaeMcBones =
+    "a bones filter's outputs are lengths and direction cosines, and direction cosines do not average";
+
+// Why a filter cannot run over sequences of U3 values per frame (U3 < 0: of any width), in the
+// order every caller reports it
+enum VaeSeqFault { VAE_SEQ_OK, VAE_SEQ_BONES, VAE_SEQ_SHAPE, VAE_SEQ_LDS };
+VaeSeqFault vae_seq_fault(const VaePlan& p, int32_t U3) {
+  if (p.shape.kind != P3D_VAE_KIND_ELBO) return VAE_SEQ_BONES;
+  if (p.wide || (U3 >= 0 && p.desc.out != U3) || p.desc.in % p.desc.out != 0 ||
+      p.desc.in / p.desc.out > P3D_VAE_SEQ_MAX_LEN)
+    return VAE_SEQ_SHAPE;
+  return p.seq_lds ? VAE_SEQ_OK : VAE_SEQ_LDS;
+}
+
+// The checks and the VaeSeqArgs of the two sequence-filter calls.  bones: the caller's words for a
+// bones filter; ptrs: its alignment list by name (the K-sample form's has ref_var, else null here).
+int vae_seq_args(const char* what, const char* bones, const char* ptrs, p3d_vae* v, const float* pred,
+                 const int64_t* seq_off, int64_t S, int64_t N, const float* eps, uint64_t ctr, int64_t eps_row0,
+                 const float* target, float* state, int32_t* started, float* ref, const float* ref_var, float* frame_err,
+                 double* seq_err, VaeSeqArgs& a) {
+  auto bad = [what](const std::string& msg) { return fail(P3D_ERR_ARG, what + (": " + msg)); };
+  if (!v || !pred || !seq_off || !ref) return bad("null argument");
+  const VaePlan& p = v->plan;
+  const VaeSeqFault f = vae_seq_fault(p, -1);
+  if (f == VAE_SEQ_BONES) return bad(bones);
+  if (f == VAE_SEQ_SHAPE)
+    return bad("in must be seq_len * out with seq_len in 1 .. " + std::to_string(P3D_VAE_SEQ_MAX_LEN));
+  if (f == VAE_SEQ_LDS) return bad("parameters, one tile and the state tile exceed a workgroup's LDS");
+  if (S < 1 || S > (1 << 20)) return bad("S must be in 1 .. 2^20");
+  if (N < 1 || N > (1 << 20)) return bad("N must be in 1 .. 2^20");
+  if (eps_row0 < 0) return bad("eps_row0 must be >= 0");
+  if ((state != nullptr) != (started != nullptr)) return bad("state and started go together");
+  if ((frame_err || seq_err) && !target) return bad("frame_err and seq_err need a target");
+  for (const void* q : {(const void*)pred, (const void*)eps, (const void*)target, (const void*)state, (const void*)ref,
+                        (const void*)ref_var})
+    if ((uintptr_t)q % 16 != 0) return bad(ptrs + std::string(" must be 16-byte aligned"));
+  a.desc = p.desc; a.desc_dev = v->d_desc; a.pk = v->pk; a.pred = pred; a.seq_off = seq_off; a.S = S; a.N = N;
+  a.eps = eps; a.seed = v->seed; a.ctr = ctr; a.eps_row0 = eps_row0; a.target = target;
+  a.state = state; a.started = started; a.ref = ref; a.frame_err = frame_err; a.seq_err = seq_err;
+  a.seq_len = p.seq_len; a.xoff = p.seq_xoff; a.toff = p.seq_toff; a.ldt = p.seq_ldt; a.moff = p.seq_moff;
+  return P3D_OK;
+}
+
 }  // namespace
 
 extern "C" int64_t p3d_vae_lds_bytes(int32_t in, int32_t n_enc, const int32_t* enc_dims, int32_t latent, int32_t n_dec,
@@ -552,29 +596,11 @@ extern "C" int p3d_vae_seq_filter(p3d_vae* v, const float* pred, const int64_t* 
                                   const float* eps, uint64_t ctr, int64_t eps_row0, const float* target,
                                   float* state, int32_t* started, float* ref, float* frame_err, double* seq_err,
                                   void* stream) {
-  if (!v || !pred || !seq_off || !ref) return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: null argument");
-  const VaePlan& p = v->plan;
-  if (p.shape.kind != P3D_VAE_KIND_ELBO) return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: a bones filter has no sequence form");
-  if (p.wide || p.desc.in % p.desc.out != 0 || p.desc.in / p.desc.out > P3D_VAE_SEQ_MAX_LEN)
-    return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: in must be seq_len * out with seq_len in 1 .. " +
-                                 std::to_string(P3D_VAE_SEQ_MAX_LEN));
-  if (!p.seq_lds)
-    return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: parameters, one tile and the state tile exceed a workgroup's LDS");
-  if (S < 1 || S > (1 << 20)) return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: S must be in 1 .. 2^20");
-  if (N < 1 || N > (1 << 20)) return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: N must be in 1 .. 2^20");
-  if (eps_row0 < 0) return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: eps_row0 must be >= 0");
-  if ((state != nullptr) != (started != nullptr))
-    return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: state and started go together");
-  if ((frame_err || seq_err) && !target)
-    return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: frame_err and seq_err need a target");
-  for (const void* q : {(const void*)pred, (const void*)eps, (const void*)target, (const void*)state, (const void*)ref})
-    if ((uintptr_t)q % 16 != 0)
-      return fail(P3D_ERR_ARG, "p3d_vae_seq_filter: pred, eps, target, state and ref must be 16-byte aligned");
   VaeSeqArgs a{};
-  a.desc = p.desc; a.desc_dev = v->d_desc; a.pk = v->pk; a.pred = pred; a.seq_off = seq_off; a.S = S; a.N = N;
-  a.eps = eps; a.seed = v->seed; a.ctr = ctr; a.eps_row0 = eps_row0; a.target = target;
-  a.state = state; a.started = started; a.ref = ref; a.frame_err = frame_err; a.seq_err = seq_err;
-  a.seq_len = p.seq_len; a.xoff = p.seq_xoff; a.toff = p.seq_toff; a.ldt = p.seq_ldt; a.moff = p.seq_moff;
+  if (int rc = vae_seq_args("p3d_vae_seq_filter", "a bones filter has no sequence form", "pred, eps, target, state and ref",
+                            v, pred, seq_off, S, N, eps, ctr, eps_row0, target, state, started, ref, nullptr, frame_err,
+                            seq_err, a))
+    return rc;
   return vae_launch(v, vae_kernel_index(VF_SEQ, P3D_VAE_KIND_ELBO, 0, 0, v->seq_form ? 4 : 1), (unsigned)((S + 15) / 16),
                     stream, a);
 }
@@ -594,9 +620,7 @@ int vae_mc_check(const void* out, const char* out_name, int32_t K, uint64_t ctr,
 }
 
 int vae_mc_bones(const p3d_vae* v, const char* what) {
-  if (v->plan.shape.kind != P3D_VAE_KIND_ELBO)
-    return fail(P3D_ERR_ARG, std::string(what) + ": a bones filter's outputs are lengths and direction cosines, "
-                                                 "and direction cosines do not average");
+  if (v->plan.shape.kind != P3D_VAE_KIND_ELBO) return fail(P3D_ERR_ARG, what + (": " + std::string(kVaeMcBones)));
   return P3D_OK;
 }
 
@@ -642,31 +666,10 @@ extern "C" int p3d_vae_seq_filter_mc(p3d_vae* v, const float* pred, const int64_
                                      double* seq_err, void* stream) {
   const char* what = "p3d_vae_seq_filter_mc";
   if (int rc = vae_mc_check(ref, "ref", K, ctr, what)) return rc;
-  if (!v || !pred || !seq_off) return fail(P3D_ERR_ARG, "p3d_vae_seq_filter_mc: null argument");
-  const VaePlan& p = v->plan;
-  if (int rc = vae_mc_bones(v, what)) return rc;
-  if (p.wide || p.desc.in % p.desc.out != 0 || p.desc.in / p.desc.out > P3D_VAE_SEQ_MAX_LEN)
-    return fail(P3D_ERR_ARG, "p3d_vae_seq_filter_mc: in must be seq_len * out with seq_len in 1 .. " +
-                                 std::to_string(P3D_VAE_SEQ_MAX_LEN));
-  if (!p.seq_lds)
-    return fail(P3D_ERR_ARG, "p3d_vae_seq_filter_mc: parameters, one tile and the state tile exceed a workgroup's LDS");
-  if (S < 1 || S > (1 << 20)) return fail(P3D_ERR_ARG, "p3d_vae_seq_filter_mc: S must be in 1 .. 2^20");
-  if (N < 1 || N > (1 << 20)) return fail(P3D_ERR_ARG, "p3d_vae_seq_filter_mc: N must be in 1 .. 2^20");
-  if (eps_row0 < 0) return fail(P3D_ERR_ARG, "p3d_vae_seq_filter_mc: eps_row0 must be >= 0");
-  if ((state != nullptr) != (started != nullptr))
-    return fail(P3D_ERR_ARG, "p3d_vae_seq_filter_mc: state and started go together");
-  if ((frame_err || seq_err) && !target)
-    return fail(P3D_ERR_ARG, "p3d_vae_seq_filter_mc: frame_err and seq_err need a target");
-  for (const void* q : {(const void*)pred, (const void*)eps, (const void*)target, (const void*)state, (const void*)ref,
-                        (const void*)ref_var})
-    if ((uintptr_t)q % 16 != 0)
-      return fail(P3D_ERR_ARG, "p3d_vae_seq_filter_mc: pred, eps, target, state, ref and ref_var must be 16-byte aligned");
   VaeSeqMcArgs m{};
-  VaeSeqArgs& a = m.s;
-  a.desc = p.desc; a.desc_dev = v->d_desc; a.pk = v->pk; a.pred = pred; a.seq_off = seq_off; a.S = S; a.N = N;
-  a.eps = eps; a.seed = v->seed; a.ctr = ctr; a.eps_row0 = eps_row0; a.target = target;
-  a.state = state; a.started = started; a.ref = ref; a.frame_err = frame_err; a.seq_err = seq_err;
-  a.seq_len = p.seq_len; a.xoff = p.seq_xoff; a.toff = p.seq_toff; a.ldt = p.seq_ldt; a.moff = p.seq_moff;
+  if (int rc = vae_seq_args(what, kVaeMcBones, "pred, eps, target, state, ref and ref_var", v, pred, seq_off, S, N, eps, ctr,
+                            eps_row0, target, state, started, ref, ref_var, frame_err, seq_err, m.s))
+    return rc;
   m.ref_var = ref_var; m.K = K;
   return vae_launch(v, vae_kernel_index(VF_SEQMC, P3D_VAE_KIND_ELBO, 0, 0, 4), (unsigned)((S + 15) / 16), stream, m);
 }

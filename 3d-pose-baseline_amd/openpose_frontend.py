@@ -74,7 +74,63 @@ def lift(model, raw, mean2, std2, use2, mean3, std3, use3, out):
     return out
 
 
-class FrameLifter:
+def lift_layout(head, rows, U2, U3, with_filter=False):
+    """Byte offsets (x, y, ref, total) of a lift call's workspace: behind the path's `head` bytes
+    x [rows, U2] | y [rows, U3] | with a filter ref [rows, U3], float32, each 256-aligned -- the
+    mirror of LiftLayout (csrc/p3d_clip_host.h)."""
+    a256 = lambda b: (b + 255) // 256 * 256   # noqa: E731
+    y = head + a256(rows * U2 * 4)
+    ref = y + a256(rows * U3 * 4)
+    return head, y, ref, ref + (a256(rows * U3 * 4) if with_filter else 0)
+
+
+def _aligned_workspace(torch, nbytes, dev):
+    """`nbytes` device bytes -> (the tensor that owns them, their 256-byte aligned address)."""
+    t = torch.empty((nbytes + 256,), dtype=torch.uint8, device=dev)
+    return t, (t.data_ptr() + 255) // 256 * 256
+
+
+def _check_filter(vae, samples, out_size, who):
+    """A lifter's filter arguments: a sequence filter (ValueError: bones, wide, not a sequence
+    filter) of the lifter's width -> K, the number of draws (0: one draw, no variance)."""
+    vae._seq_len()
+    if vae.human_3d_size != out_size:
+        raise ValueError("the filter refines %d values per frame, the lifter predicts %d" % (vae.human_3d_size, out_size))
+    return 0 if samples is None else vae._samples(samples, who)
+
+
+class _Lifter:
+    """What the three lifters share: the statistics on the device and the result dicts."""
+
+    def _load_stats(self, who, model, data_mean_2d, data_std_2d, dim_to_use_2d, data_mean_3d, data_std_3d,
+                    dim_to_ignore_3d, wide=True, upload=True):
+        """Check the statistics against the model (wide: and for the 64 / 96 columns of the clip
+        kernels) and upload them (upload=False: the checks alone): m2 s2 m3 s3 (float64), u2 u3 (int32
+        dimension sets).  Returns D3."""
+        D3 = int(np.asarray(data_mean_3d).shape[0])
+        use3 = np.setdiff1d(np.arange(D3), np.asarray(dim_to_ignore_3d, np.int64))
+        if wide and (D3 != 96 or np.asarray(data_mean_2d).shape[0] != 64):
+            raise ValueError("%s: needs the 64-wide 2D and 96-wide 3D statistics" % who)
+        if len(use3) != model.output_size or len(dim_to_use_2d) != model.input_size:
+            raise ValueError("statistics do not match the model's %d inputs / %d outputs"
+                             % (model.input_size, model.output_size))
+        if not upload:
+            return D3
+        with self.torch.cuda.device(model.device):
+            self.m2, self.s2 = dp.as_device(data_mean_2d), dp.as_device(data_std_2d)
+            self.m3, self.s3 = dp.as_device(data_mean_3d), dp.as_device(data_std_3d)
+            self.u2 = dp._dims(dim_to_use_2d, 64, who)
+            self.u3 = dp._dims(use3, D3, who)
+        return D3
+
+    @staticmethod
+    def _results(off, views):
+        """Result rows -> one dict of copies per row range [off[i], off[i + 1]) (None: an empty
+        range).  views: [(key, rows as a numpy array, e.g. a pinned tensor's view)]."""
+        return [{k: v[a:b].copy() for k, v in views} if b > a else None for a, b in zip(off[:-1], off[1:])]
+
+
+class FrameLifter(_Lifter):
     """Lift mapped OpenPose frames to 3D (mm) with a LinearModel: one p3d_lift launch per call on
     pinned host rows (fp32 models; bf16 models: one HIP graph of the three calls per call)."""
 
@@ -85,16 +141,9 @@ class FrameLifter:
         if self.B < 1 or self.B > model.max_batch:
             raise ValueError("batch must be in [1, max_batch=%d]" % model.max_batch)
         dev = model.device
-        D3 = int(np.asarray(data_mean_3d).shape[0])
-        use3 = np.setdiff1d(np.arange(D3), np.asarray(dim_to_ignore_3d, np.int64))
-        if len(use3) != model.output_size or len(dim_to_use_2d) != model.input_size:
-            raise ValueError("statistics do not match the model's %d inputs / %d outputs"
-                             % (model.input_size, model.output_size))
+        D3 = self._load_stats("FrameLifter", model, data_mean_2d, data_std_2d, dim_to_use_2d, data_mean_3d, data_std_3d,
+                              dim_to_ignore_3d, wide=False)
         with torch.cuda.device(dev):
-            self.m2, self.s2 = dp.as_device(data_mean_2d), dp.as_device(data_std_2d)
-            self.m3, self.s3 = dp.as_device(data_mean_3d), dp.as_device(data_std_3d)
-            self.u2 = dp._dims(dim_to_use_2d, 64, "FrameLifter")
-            self.u3 = dp._dims(use3, D3, "FrameLifter")
             f32, f64 = torch.float32, torch.float64
             self.hin = torch.empty((self.B, 64), dtype=f64, pin_memory=True)
             self.hout = torch.empty((self.B, D3), dtype=f64, pin_memory=True)
@@ -307,7 +356,7 @@ def export_unfiltered(out_dir, frame_numbers, poses):
     return path
 
 
-class ClipLifter:
+class ClipLifter(_Lifter):
     """Lift whole OpenPose clips of up to `max_frames` frames with a float32 LinearModel: pinned
     rows in, ONE p3d_clip_lift (smoothing, mapping, forward tiles, post-processing), pinned rows
     out."""
@@ -322,19 +371,10 @@ class ClipLifter:
             raise ValueError("ClipLifter: float32 models only")
         if not 1 <= self.max_frames <= 1 << 20:
             raise ValueError("max_frames must be in [1, 2^20]")
-        D3 = int(np.asarray(data_mean_3d).shape[0])
-        use3 = np.setdiff1d(np.arange(D3), np.asarray(dim_to_ignore_3d, np.int64))
-        if D3 != 96 or np.asarray(data_mean_2d).shape[0] != 64:
-            raise ValueError("ClipLifter: needs the 64-wide 2D and 96-wide 3D statistics")
-        if len(use3) != model.output_size or len(dim_to_use_2d) != model.input_size:
-            raise ValueError("statistics do not match the model's %d inputs / %d outputs"
-                             % (model.input_size, model.output_size))
+        self._load_stats("ClipLifter", model, data_mean_2d, data_std_2d, dim_to_use_2d, data_mean_3d, data_std_3d,
+                         dim_to_ignore_3d)
         dev, n = model.device, self.max_frames
         with torch.cuda.device(dev):
-            self.m2, self.s2 = dp.as_device(data_mean_2d), dp.as_device(data_std_2d)
-            self.m3, self.s3 = dp.as_device(data_mean_3d), dp.as_device(data_std_3d)
-            self.u2 = dp._dims(dim_to_use_2d, 64, "ClipLifter")
-            self.u3 = dp._dims(use3, D3, "ClipLifter")
             f64 = torch.float64
             self.hin = torch.empty((n, 36), dtype=f64, pin_memory=True)
             self.hxy = torch.empty((n, 36), dtype=f64, pin_memory=True)
@@ -345,8 +385,7 @@ class ClipLifter:
             self.dout = torch.empty((n, 96), dtype=f64, device=dev)
             self.dsrc = torch.empty((n,), dtype=torch.int32, device=dev)
             self.work_bytes = int(_p3d.lib().p3d_clip_lift_workspace(n, model.input_size, model.output_size))
-            self.work = torch.empty((self.work_bytes + 256,), dtype=torch.uint8, device=dev)
-        self.work_ptr = (self.work.data_ptr() + 255) // 256 * 256
+            self.work, self.work_ptr = _aligned_workspace(torch, self.work_bytes, dev)
         # the batched call's offsets, workspace and optional outputs (set_offsets, _clips_buffers)
         self._off, self._clips, self.hoff, self.doff = None, None, None, None
         self.cwork, self.cwork_ptr, self.cwork_bytes = None, 0, 0
@@ -366,10 +405,9 @@ class ClipLifter:
         lift of n frames left in the workspace (behind the scan's summaries and the input rows);
         n=None: the rows of the last lift_clips / lift_clips_device, all clips one after another."""
         import _p3d
-        a256 = lambda b: (b + 255) // 256 * 256   # noqa: E731
         if n is None:
             return self._clips_rows(0)
-        off = int(_p3d.lib().p3d_clip_workspace(n)) + a256(n * self.model.input_size * 4)
+        off = lift_layout(int(_p3d.lib().p3d_clip_workspace(n)), n, self.model.input_size, self.model.output_size)[1]
         return _p3d.device_view(self.work_ptr + off, (n, self.model.output_size), self.model.device.index)
 
     # ------------------------------------------------------------------ a batch of clips
@@ -381,9 +419,8 @@ class ClipLifter:
         S, N, filtered = self._clips
         if area == 1 and not filtered:
             raise ValueError("the last batched lift ran without a filter")
-        a256 = lambda b: (b + 255) // 256 * 256   # noqa: E731
-        off = (int(_p3d.lib().p3d_clips_workspace(N, S)) + a256(N * self.model.input_size * 4)
-               + area * a256(N * self.model.output_size * 4))
+        off = lift_layout(int(_p3d.lib().p3d_clips_workspace(N, S)), N, self.model.input_size, self.model.output_size,
+                          filtered)[1 + area]
         return _p3d.device_view(self.cwork_ptr + off, (N, self.model.output_size), self.model.device.index)
 
     def refined_rows(self):
@@ -422,8 +459,7 @@ class ClipLifter:
                                                        int(filtered)))
         with torch.cuda.device(dev):
             if self.cwork is None or need > self.cwork_bytes:
-                self.cwork = torch.empty((need + 256,), dtype=torch.uint8, device=dev)
-                self.cwork_ptr = (self.cwork.data_ptr() + 255) // 256 * 256
+                self.cwork, self.cwork_ptr = _aligned_workspace(torch, need, dev)
                 self.cwork_bytes = need
             if unfiltered and self.dout_u is None:
                 self.hout_u = torch.empty((n, 96), dtype=torch.float64, pin_memory=True)
@@ -449,12 +485,7 @@ class ClipLifter:
             if samples is not None or eps is not None or unfiltered:
                 raise ValueError("samples, eps and unfiltered need a filter (vae=...)")
         else:
-            vae._seq_len()                                   # (ValueError: bones, wide, not a sequence filter)
-            if vae.human_3d_size != self.model.output_size:
-                raise ValueError("the filter refines %d values per frame, the lifter predicts %d"
-                                 % (vae.human_3d_size, self.model.output_size))
-            if samples is not None:
-                K = vae._samples(samples, "lift_clips")
+            K = _check_filter(vae, samples, self.model.output_size, "lift_clips")
             if eps is not None and (tuple(eps.shape) != ((K, N, vae.latent_dim) if K else (N, vae.latent_dim))
                                     or eps.dtype != self.torch.float32 or not eps.is_cuda or not eps.is_contiguous()):
                 raise ValueError("eps: expected a contiguous float32 device tensor %s"
@@ -517,19 +548,14 @@ class ClipLifter:
                 h[:N].copy_(d[:N], non_blocking=True)
             torch.cuda.current_stream(self.model.device).synchronize()
         self.model.check_errors()
-        out = []
-        for s in range(len(rows)):
-            a, b = int(off[s]), int(off[s + 1])
-            local = lambda t: np.where(t[a:b] >= 0, t[a:b] - a, -1).astype(np.int32)   # noqa: E731
-            d = {"poses": self.hout.numpy()[a:b].copy(), "xy_s": self.hxy.numpy()[a:b].copy(),
-                 "src": local(self.hsrc.numpy())}
-            if unfiltered:
-                d["poses_unfiltered"] = self.hout_u.numpy()[a:b].copy()
-                d["src_unfiltered"] = local(self.hsrc_u.numpy())
-            if K:
-                d["ref_var"] = self.hvar.numpy()[a:b].copy()
-            out.append(d)
-        return out
+        first = np.repeat(off[:-1], np.diff(off))            # every row's clip start: 'src' counts from it (-1 stays)
+        local = lambda t: np.where(t.numpy()[:N] >= 0, t.numpy()[:N] - first, -1).astype(np.int32)   # noqa: E731
+        views = [("poses", self.hout.numpy()), ("xy_s", self.hxy.numpy()), ("src", local(self.hsrc))]
+        if unfiltered:
+            views += [("poses_unfiltered", self.hout_u.numpy()), ("src_unfiltered", local(self.hsrc_u))]
+        if K:
+            views.append(("ref_var", self.hvar.numpy()))
+        return self._results(off.tolist(), views)
 
     def lift_clip(self, xy, smooth=True):
         """xy [N <= max_frames, 36] raw keypoints in position order -> (poses [N, 96] float64 mm,
@@ -557,7 +583,7 @@ class ClipLifter:
 # --------------------------------------------------------------------------------------
 
 
-class LiveLifter:
+class LiveLifter(_Lifter):
     """Lift up to `slots` live OpenPose streams frame by frame with a float32 LinearModel.  Every
     tick (``push``) takes at most one raw frame (36 values) per open slot and returns the rows that
     became final: with smoothing frame f once frame f + 4 has arrived (frames 0 .. 4 together at
@@ -582,33 +608,20 @@ class LiveLifter:
             raise ValueError("LiveLifter: float32 models only")
         if not 1 <= self.S <= 1 << 16:
             raise ValueError("slots must be in [1, 2^16]")
-        D3 = int(np.asarray(data_mean_3d).shape[0])
-        use3 = np.setdiff1d(np.arange(D3), np.asarray(dim_to_ignore_3d, np.int64))
-        if D3 != 96 or np.asarray(data_mean_2d).shape[0] != 64:
-            raise ValueError("LiveLifter: needs the 64-wide 2D and 96-wide 3D statistics")
-        if len(use3) != model.output_size or len(dim_to_use_2d) != model.input_size:
-            raise ValueError("statistics do not match the model's %d inputs / %d outputs"
-                             % (model.input_size, model.output_size))
+        stats = (data_mean_2d, data_std_2d, dim_to_use_2d, data_mean_3d, data_std_3d, dim_to_ignore_3d)
+        self._load_stats("LiveLifter", model, *stats, upload=False)   # (the filter is vetted before anything is uploaded)
         self.K = 0
         if vae is None:
             if samples is not None:
                 raise ValueError("samples needs a filter (vae=...)")
         else:
-            vae._seq_len()                                   # (ValueError: bones, wide, not a sequence filter)
-            if vae.human_3d_size != model.output_size:
-                raise ValueError("the filter refines %d values per frame, the lifter predicts %d"
-                                 % (vae.human_3d_size, model.output_size))
-            if samples is not None:
-                self.K = vae._samples(samples, "LiveLifter")
+            self.K = _check_filter(vae, samples, model.output_size, "LiveLifter")
             self.ctr = vae._calls + 1                        # the session's noise counter(s), as a fresh
             vae._calls += self.K or 1                        # filter_sequences call takes them
+        self._load_stats("LiveLifter", model, *stats)
         S, cap, dev, U3 = self.S, 5 * self.S, model.device, model.output_size
         lib = _p3d.lib()
         with torch.cuda.device(dev):
-            self.m2, self.s2 = dp.as_device(data_mean_2d), dp.as_device(data_std_2d)
-            self.m3, self.s3 = dp.as_device(data_mean_3d), dp.as_device(data_std_3d)
-            self.u2 = dp._dims(dim_to_use_2d, 64, "LiveLifter")
-            self.u3 = dp._dims(use3, D3, "LiveLifter")
             pin = lambda shape, dt: torch.zeros(shape, dtype=dt, pin_memory=True)   # noqa: E731
             i32, f64 = torch.int32, torch.float64
             # the tick's table and the rows in and out: pinned, read and written by the kernels in place
@@ -619,15 +632,17 @@ class LiveLifter:
             self.hvar = pin((cap, U3), torch.float32) if self.K else None
             self.state = torch.empty((int(lib.p3d_live_state_bytes(S, U3)),), dtype=torch.uint8, device=dev)
             self.work_bytes = int(lib.p3d_live_push_workspace(S, model.input_size, U3, int(vae is not None)))
-            self.work = torch.empty((self.work_bytes + 256,), dtype=torch.uint8, device=dev)
+            self.work, self.work_ptr = _aligned_workspace(torch, self.work_bytes, dev)
             self.fstate, self.fstarted = vae.new_seq_state(S) if vae is not None else (None, None)
             _p3d.check(lib.p3d_live_reset(self.state.data_ptr(), S, -1, model.stream()), "p3d_live_reset")
-        self.work_ptr = (self.work.data_ptr() + 255) // 256 * 256
         self.count = np.zeros(S, np.int32)                   # frames received per slot
         self._push, self._close, self._short = np.zeros(S, np.uint8), np.zeros(S, np.uint8), np.zeros(S, np.int32)
         self.is_open = np.zeros(S, bool)
         self.emitted = 0                                     # rows emitted so far: the tick's eps_row0
         self.hin_np = self.hin.numpy()
+        # the result rows' numpy views, taken once: push slices them per slot
+        self._views = [(k, t.numpy()) for k, t in (("frames", self.hframe), ("poses", self.hout), ("xy_s", self.hxy),
+                                                   ("src", self.hsrc), ("ref_var", self.hvar)) if t is not None]
 
     def latency(self):
         """Pushes between a frame and its row: 4 with smoothing, 0 without."""
@@ -705,17 +720,7 @@ class LiveLifter:
                 _p3d.check(rc, "p3d_host_wait")
         self.emitted += N
         self.is_open[closing] = False
-        off = self.hoff.numpy()
-        out = {}
-        for s in range(S):
-            a, b = int(off[s]), int(off[s + 1])
-            if b > a:
-                d = {"frames": self.hframe.numpy()[a:b].copy(), "poses": self.hout.numpy()[a:b].copy(),
-                     "xy_s": self.hxy.numpy()[a:b].copy(), "src": self.hsrc.numpy()[a:b].copy()}
-                if self.K:
-                    d["ref_var"] = self.hvar.numpy()[a:b].copy()
-                out[s] = d
-        return out
+        return {s: d for s, d in enumerate(self._results(self.hoff.numpy().tolist(), self._views)) if d}
 
     def close(self, slot):
         """End the slot's stream: the rows that were still waiting for their window (the last four

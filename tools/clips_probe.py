@@ -49,7 +49,6 @@ def timed(fn, reps):
 def per_clip_loop(cl, vae, K, off, ctr):
     """The existing calls clip by clip on slices of the lifter's device buffers; returns the pass."""
     lib, m = _p3d.lib(), cl.model
-    a256 = lambda b: (b + 255) // 256 * 256   # noqa: E731
     S = len(off) - 1
     pairs = torch.tensor([[0, int(off[s + 1] - off[s])] for s in range(S)], dtype=torch.int64, device=m.device)
     ref = torch.empty((int(off[-1]), 48), dtype=torch.float32, device=m.device)
@@ -62,7 +61,7 @@ def per_clip_loop(cl, vae, K, off, ctr):
         outs = (cl.dxy.data_ptr() + a * 288, cl.dout.data_ptr() + a * 768, cl.dsrc.data_ptr() + a * 4)
         lift = (m._h, cl.din.data_ptr() + a * 288, n, 1) + st + outs + (cl.work_ptr, cl.work_bytes)
         wb = int(lib.p3d_clip_workspace(n))
-        y = cl.work_ptr + wb + a256(n * m.input_size * 4)
+        y = cl.work_ptr + of.lift_layout(wb, n, m.input_size, m.output_size)[1]
         r = ref.data_ptr() + a * 192
         flt = (vae._h, y, pairs.data_ptr() + 16 * s, 1, n) if vae is not None else None
         fin = (r, n, outs[0]) + st[4:] + outs[1:] + (cl.work_ptr, wb)
