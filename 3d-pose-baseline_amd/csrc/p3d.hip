@@ -23,6 +23,7 @@
 #include "p3d_clip.h"
 #include "p3d_clips.h"
 #include "p3d_live.h"
+#include "p3d_skel.h"
 #include "p3d_serve.h"
 #include "p3d_serve6.h"
 #include "p3d_serve_plan.h"
@@ -63,5 +64,7 @@
 #include "p3d_clip_host.h"
 #include "p3d_clips_host.h"
 #include "p3d_live_host.h"
+// Lifted rows as a rigid skeleton: bone lengths, rotations, rigid pose (kernels in p3d_skel.h)
+#include "p3d_skel_host.h"
 
 #include "p3d_dp.h"

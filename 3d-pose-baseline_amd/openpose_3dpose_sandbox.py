@@ -22,12 +22,15 @@ immediate subdirectory with frame files, exported to ``<out_dir>/<clip name>/``)
 ``3d_pose_vae_filter_kin.py`` saves (``--latent_dim`` / ``--enc_dim`` / ``--dec_dim`` as there),
 between the forward and the post-processing, every clip a fresh sequence; ``--filter_samples K``
 averages K posterior samples per frame; ``--export_unfiltered`` also writes
-``3d_data_unfiltered.json``, the poses without the filter.  Without these flags the driver does
-what it did before them.
+``3d_data_unfiltered.json``, the poses without the filter.  ``--export_bvh`` also writes
+``skeleton.bvh`` beside ``3d_data.json`` (``ClipLifter.skeleton``: constant bone lengths per clip,
+one rotation per bone and frame; ``--bvh_fps`` its frame rate; the 17-joint models only).  Without
+these flags the driver does what it did before them.
 """
 from __future__ import annotations
 
 import logging
+import os
 import sys
 
 import numpy as np
@@ -73,6 +76,12 @@ def load_filter(flags, model):
     return vae
 
 
+def write_bvh(flags, out_dir, frame_numbers, sk):
+    """--export_bvh of one clip: <out_dir>/skeleton.bvh from a ClipLifter.skeleton / skeleton_rows dict."""
+    return of.export_bvh(os.path.join(out_dir, "skeleton.bvh"), frame_numbers, sk["lengths"], sk["euler"], sk["root"],
+                         fps=flags.bvh_fps)
+
+
 def run_clips(flags):
     """--clips_root / --vae_filter: one p3d_clips_lift over every clip."""
     if flags.clips_root:
@@ -93,6 +102,7 @@ def run_clips(flags):
         logger.info("lifting %d clips, %d frames", len(clips), sum(len(c) for c in clips))
         results = lifter.lift_clips(clips, smooth=smooth, vae=vae, samples=flags.filter_samples,
                                     unfiltered=flags.export_unfiltered)
+        skeletons = lifter.skeleton() if flags.export_bvh else None
         if vae is not None:
             vae.close()
         model.close()
@@ -101,8 +111,13 @@ def run_clips(flags):
         paths = of.export_maya(flags.out_dir, numbers[0], r["poses"], r["xy_s"])
         if flags.export_unfiltered:
             paths += (of.export_unfiltered(flags.out_dir, numbers[0], r["poses_unfiltered"]),)
+        if skeletons:
+            paths += (write_bvh(flags, flags.out_dir, numbers[0], skeletons[0]),)
     else:
         paths = of.export_maya_clips(flags.out_dir, names, numbers, results, unfiltered=flags.export_unfiltered)
+        if skeletons:
+            bvh = of.export_bvh_clips(flags.out_dir, names, numbers, skeletons, fps=flags.bvh_fps)
+            paths = [q + (b,) for q, b in zip(paths, bvh)]
     logger.info("exported maya json under %s", flags.out_dir)
     logger.info("Done!")
     return paths
@@ -117,6 +132,8 @@ def run(flags):
                                3: logging.DEBUG}.get(flags.verbose, logging.INFO))
     if (flags.filter_samples is not None or flags.export_unfiltered) and not flags.vae_filter:
         raise SystemExit("--filter_samples and --export_unfiltered need --vae_filter")
+    if flags.export_bvh and flags.predict_14:
+        raise SystemExit("--export_bvh needs the 17-joint model: the skeleton's bones are not defined for --predict_14")
     if flags.clips_root or flags.vae_filter:
         return run_clips(flags)
     logger.info("start reading json files")
@@ -136,8 +153,11 @@ def run(flags):
         held = int((src != np.arange(len(src))).sum())
         if held:
             logger.info("%d failed frames replaced by the last good one", held)
+        sk = lifter.skeleton()[0] if flags.export_bvh else None
         model.close()
     paths = of.export_maya(flags.out_dir, frame_numbers, poses, xy_s)
+    if sk is not None:
+        paths += (write_bvh(flags, flags.out_dir, frame_numbers, sk),)
     for path in paths:
         logger.info("exported maya json to %s", path)
     logger.info("Done!")

@@ -16,7 +16,8 @@ skips frame 0.  This driver follows the clip pipeline instead: the poses of the 
 ``openpose_3dpose_sandbox.py`` on the same directory.
 
 After ``--idle_exit SECONDS`` without a new frame the stream is closed, the last four frames are
-flushed and ``export_maya`` writes ``3d_data.json`` / ``2d_data.json`` into ``--out_dir``.
+flushed and ``export_maya`` writes ``3d_data.json`` / ``2d_data.json`` into ``--out_dir``; with
+``--export_bvh`` the stream's collected rows also go through ``skeleton_rows`` into ``skeleton.bvh``.
 ``--no_smooth`` lifts every frame at once.  A frame file that cannot be parsed yet (still being
 written) is tried again at the next poll; a gap in the frame numbers is waited for and, if it is
 still there at the idle exit, refused like the clip driver refuses it.
@@ -128,6 +129,8 @@ def run(flags):
         raise SystemExit("--clips_root and --export_unfiltered belong to openpose_3dpose_sandbox.py")
     if flags.filter_samples is not None and not flags.vae_filter:
         raise SystemExit("--filter_samples needs --vae_filter")
+    if flags.export_bvh and flags.predict_14:
+        raise SystemExit("--export_bvh needs the 17-joint model: the skeleton's bones are not defined for --predict_14")
     logging.basicConfig(level={0: logging.ERROR, 1: logging.WARNING, 2: logging.INFO,
                                3: logging.DEBUG}.get(flags.verbose, logging.INFO))
     logger.info("the pose plots and the cv2 window are not part of this build")
@@ -152,6 +155,9 @@ def run(flags):
     if held:
         logger.info("%d failed frames replaced by the last good one", held)
     paths = of.export_maya(flags.out_dir, numbers, poses, xy_s)
+    if flags.export_bvh:
+        sk = of.skeleton_rows(poses, src, [0, len(numbers)], device=model.device)[0]
+        paths += (sandbox.write_bvh(flags, flags.out_dir, numbers, sk),)
     for path in paths:
         logger.info("exported maya json to %s", path)
     logger.info("Done!")

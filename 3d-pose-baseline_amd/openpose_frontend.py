@@ -356,6 +356,191 @@ def export_unfiltered(out_dir, frame_numbers, poses):
     return path
 
 
+# --------------------------------------------------------------------------------------
+# lifted rows as a rigid skeleton: bone lengths, rotations, BVH
+# --------------------------------------------------------------------------------------
+
+SKEL_H36M = (0, 1, 2, 3, 6, 7, 8, 12, 13, 14, 15, 17, 18, 19, 25, 26, 27)   # the skeleton's joints among the 32
+
+
+def skel_tables():
+    """(names [17], ja [16], jb [16], pb [16], rest [16, 3]) of the skeleton: the bones filter's bone
+    table, every bone's parent bone (-1: it leaves the hip) and its unit rest direction, keyed by
+    the child joint -- right hip / arm bones along -X, left ones along +X, knees and feet along -Y,
+    spine to head along +Y."""
+    import data_utils
+    from top_vae_3d_pose.bones import BJA, BJB
+    names = [data_utils.H36M_NAMES[j].replace("/", "") for j in SKEL_H36M]
+    pb = [BJB.index(a) if a else -1 for a in BJA]
+    rest = np.zeros((16, 3))
+    for b, j in enumerate(BJB):
+        n = names[j]
+        if n.endswith(("Knee", "Foot")):
+            rest[b, 1] = -1.0
+        elif n[0] in "RL":
+            rest[b, 0] = -1.0 if n[0] == "R" else 1.0
+        else:
+            rest[b, 1] = 1.0
+    return names, list(BJA), list(BJB), pb, rest
+
+
+class _SkeletonBuffers:
+    """The device and pinned rows of p3d_skel_lengths / p3d_skel_pose, grown on demand (a captured
+    graph holds the addresses: size them with one eager call before capturing)."""
+
+    OUT = (("quat", (16, 4)), ("euler", (16, 3)), ("rigid", (17, 3)), ("root", (3,)))
+
+    def __init__(self, torch, device):
+        self.torch, self.device = torch, device
+        self.rows, self.clips, self.work_bytes = 0, 0, 0
+
+    def _grow(self, N, S):
+        import _p3d
+        torch, dev = self.torch, self.device
+        with torch.cuda.device(dev):
+            if N > self.rows:
+                self.d = {k: torch.empty((N,) + shp, dtype=torch.float64, device=dev) for k, shp in self.OUT}
+                self.h = {k: torch.empty((N,) + shp, dtype=torch.float64, pin_memory=True) for k, shp in self.OUT}
+                self.rows = N
+            if S > self.clips:
+                self.hoff = torch.empty((S + 1,), dtype=torch.int64, pin_memory=True)
+                self.doff = torch.empty((S + 1,), dtype=torch.int64, device=dev)
+                self.dlen, self.dmean = (torch.empty((S, 16), dtype=torch.float64, device=dev) for _ in range(2))
+                self.hlen = torch.empty((S, 16), dtype=torch.float64, pin_memory=True)
+                self.dused = torch.empty((S,), dtype=torch.int64, device=dev)
+                self.hused = torch.empty((S,), dtype=torch.int64, pin_memory=True)
+                self.clips = S
+            need = int(_p3d.lib().p3d_skel_workspace(N, S))
+            if need > self.work_bytes:
+                self.work, self.work_ptr = _aligned_workspace(torch, need, dev)
+                self.work_bytes = need
+
+    def run(self, dposes, dsrc, off, lengths=None):
+        """The two calls on device rows dposes [>= N, 96] / dsrc [>= N] int32 or None under the clip
+        offsets `off` (int64 [S + 1]) -> one dict per clip."""
+        import _p3d
+        torch, lib, p = self.torch, _p3d.lib(), _p3d.ptr
+        off = np.ascontiguousarray(off, np.int64)
+        S, N = off.shape[0] - 1, int(off[-1])
+        if lengths is not None:
+            lengths = np.asarray(lengths, np.float64)
+            if lengths.shape == (16,):
+                lengths = np.tile(lengths, (S, 1))
+            if lengths.shape != (S, 16) or not (lengths >= 0).all():
+                raise ValueError("lengths: expected [16] or [%d, 16] bone lengths >= 0, got %s" % (S, lengths.shape))
+        self._grow(N, S)
+        with torch.cuda.device(self.device):
+            st = _p3d.stream_handle()
+            self.hoff.numpy()[:S + 1] = off
+            self.doff[:S + 1].copy_(self.hoff[:S + 1], non_blocking=True)
+            _p3d.check(lib.p3d_skel_lengths(p(dposes), p(dsrc), off.ctypes.data, p(self.doff), S, N, p(self.dmean),
+                                            p(self.dused), self.work_ptr, self.work_bytes, st), "p3d_skel_lengths")
+            dlen = self.dmean
+            if lengths is not None:
+                self.hlen.numpy()[:S] = lengths
+                self.dlen[:S].copy_(self.hlen[:S], non_blocking=True)
+                dlen = self.dlen
+            _p3d.check(lib.p3d_skel_pose(p(dposes), p(dsrc), off.ctypes.data, p(self.doff), S, N, p(dlen),
+                                         *(p(self.d[k]) for k, _ in self.OUT), st), "p3d_skel_pose")
+            for k, _ in self.OUT:
+                self.h[k][:N].copy_(self.d[k][:N], non_blocking=True)
+            self.hused[:S].copy_(self.dused[:S], non_blocking=True)
+            if lengths is None:
+                self.hlen[:S].copy_(self.dmean[:S], non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+        out = _Lifter._results(off.tolist(), [(k, self.h[k].numpy()) for k, _ in self.OUT])
+        for s, r in enumerate(out):
+            r["lengths"], r["n_used"] = self.hlen.numpy()[s].copy(), int(self.hused[s])
+        return out
+
+
+def skeleton_rows(poses, src, offsets, lengths=None, device=None):
+    """The rigid skeleton of host rows: poses [N, 96] float64 as the lifters return them (or as read
+    back from ``3d_data.json``), S clips one after another under `offsets` [S + 1]; src [N]: each
+    clip's 'src' as the lifters return it (positions inside the clip, -1: zeros), concatenated, or
+    None (every row carries its own pose).  lengths: [16] or [S, 16] bone lengths to use instead of
+    the clips' own means (a known actor; a live stream's earlier estimate).  Returns one dict per
+    clip: 'lengths' [16] (the ones used), 'n_used' (the frames the clip's own mean is over), 'quat'
+    [n, 16, 4] (w, x, y, z), 'euler' [n, 16, 3] (Z, X, Y degrees), 'rigid' [n, 17, 3], 'root' [n, 3],
+    in skeleton coordinates (X, Y, Z) = (x, z, -y).  device: a torch device (default: the current one)."""
+    import torch
+    poses = np.ascontiguousarray(poses, np.float64)
+    off = np.asarray(offsets)
+    if poses.ndim != 2 or poses.shape[1] != 96 or poses.shape[0] < 1:
+        raise ValueError("expected poses [N >= 1, 96] (32 joints), got %s" % (poses.shape,))
+    if off.ndim != 1 or off.shape[0] < 2 or not np.issubdtype(off.dtype, np.integer) or off[0] != 0 \
+            or (np.diff(off) <= 0).any() or off[-1] != poses.shape[0]:
+        raise ValueError("clip offsets must be integers [S + 1] that start at 0, give every clip a frame and end at N")
+    off = off.astype(np.int64)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    with torch.cuda.device(dev):
+        dposes, dsrc = torch.from_numpy(poses).to(dev), None
+        if src is not None:
+            src = np.asarray(src)
+            if src.shape != (poses.shape[0],) or not np.issubdtype(src.dtype, np.integer):
+                raise ValueError("src: expected %d integers, got %s %s" % (poses.shape[0], src.dtype, src.shape))
+            first = np.repeat(off[:-1], np.diff(off))
+            dsrc = torch.from_numpy(np.where(src >= 0, src + first, -1).astype(np.int32)).to(dev)
+        return _SkeletonBuffers(torch, dev).run(dposes, dsrc, off, lengths)
+
+
+def export_bvh(path, frame_numbers, lengths, euler, root, fps=30.0):
+    """Write one clip as a BVH file: ``ROOT Hips`` (six channels, its rotation always zero) and one
+    ``JOINT bone_<child joint>`` per bone, placed at the bone's START (OFFSET 0 for the three hip
+    bones, else the parent bone's length times its rest direction) with channels ``Zrotation
+    Xrotation Yrotation``; every leaf ends in an ``End Site`` at its own length times its rest
+    direction.  lengths [16], euler [N, 16, 3] (Z, X, Y degrees) and root [N, 3] as skeleton_rows /
+    ClipLifter.skeleton return them; one motion line per frame, values printed with repr.  Lengths
+    that are all zero (a clip with n_used == 0) and non-finite values raise ValueError.  Returns path."""
+    lengths, euler, root = np.asarray(lengths, np.float64), np.asarray(euler, np.float64), np.asarray(root, np.float64)
+    n = len(frame_numbers)
+    if lengths.shape != (16,) or euler.shape != (n, 16, 3) or root.shape != (n, 3) or n < 1:
+        raise ValueError("%s: expected lengths [16], euler [N, 16, 3], root [N, 3] and N >= 1 frame numbers" % path)
+    if not lengths.any():
+        raise ValueError("%s: the clip has no frame to take bone lengths from (n_used == 0)" % path)
+    if not (np.isfinite(lengths).all() and np.isfinite(euler).all() and np.isfinite(root).all()):
+        raise ValueError("%s: non-finite lengths, angles or root positions" % path)
+    if not fps > 0:
+        raise ValueError("%s: fps must be > 0" % path)
+    names, _, jb, pb, rest = skel_tables()
+    vec = lambda v: " ".join(repr(float(x)) for x in v)   # noqa: E731
+    lines, order = ["HIERARCHY", "ROOT Hips", "{", "  OFFSET 0.0 0.0 0.0",
+                    "  CHANNELS 6 Xposition Yposition Zposition Zrotation Xrotation Yrotation"], []
+
+    def joint(b, depth):
+        pad = "  " * depth
+        order.append(b)
+        lines.extend([pad + "JOINT bone_" + names[jb[b]], pad + "{",
+                      pad + "  OFFSET " + vec(lengths[pb[b]] * rest[pb[b]] if pb[b] >= 0 else np.zeros(3)),
+                      pad + "  CHANNELS 3 Zrotation Xrotation Yrotation"])
+        kids = [c for c in range(16) if pb[c] == b]
+        for c in kids:
+            joint(c, depth + 1)
+        if not kids:
+            lines.extend([pad + "  End Site", pad + "  {", pad + "    OFFSET " + vec(lengths[b] * rest[b]), pad + "  }"])
+        lines.append(pad + "}")
+
+    for b in range(16):
+        if pb[b] < 0:
+            joint(b, 1)
+    lines.extend(["}", "MOTION", "Frames: %d" % n, "Frame Time: " + repr(1.0 / float(fps))])
+    for f in range(n):
+        lines.append(vec(root[f]) + " 0.0 0.0 0.0 " + vec(euler[f, order].reshape(-1)))
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    return path
+
+
+def export_bvh_clips(out_dir, names, frame_numbers, skeletons, fps=30.0):
+    """export_bvh of every clip of a ClipLifter.skeleton / skeleton_rows result into
+    <out_dir>/<clip name>/skeleton.bvh, beside export_maya_clips' files.  Returns the paths."""
+    if not len(names) == len(frame_numbers) == len(skeletons):
+        raise ValueError("expected one name, one array of frame numbers and one skeleton per clip")
+    return [export_bvh(os.path.join(out_dir, name, "skeleton.bvh"), fn, sk["lengths"], sk["euler"], sk["root"], fps)
+            for name, fn, sk in zip(names, frame_numbers, skeletons)]
+
+
 class ClipLifter(_Lifter):
     """Lift whole OpenPose clips of up to `max_frames` frames with a float32 LinearModel: pinned
     rows in, ONE p3d_clip_lift (smoothing, mapping, forward tiles, post-processing), pinned rows
@@ -390,6 +575,7 @@ class ClipLifter(_Lifter):
         self._off, self._clips, self.hoff, self.doff = None, None, None, None
         self.cwork, self.cwork_ptr, self.cwork_bytes = None, 0, 0
         self.hout_u, self.hsrc_u, self.dout_u, self.dsrc_u, self.hvar, self.dvar = (None,) * 6
+        self._last_off, self._skel = None, None              # the last lift's clip offsets; skeleton()'s buffers
 
     def lift_device(self, n, smooth=True):
         """p3d_clip_lift of the first n rows of self.din into self.dxy / dout / dsrc (current stream)."""
@@ -399,6 +585,7 @@ class ClipLifter(_Lifter):
             self.model._h, p(self.din), n, int(bool(smooth)), p(self.m2), p(self.s2), p(self.u2), self.u2.numel(),
             p(self.m3), p(self.s3), p(self.u3), self.u3.numel(), 96, int(self.cache_on_fail), p(self.dxy),
             p(self.dout), p(self.dsrc), self.work_ptr, self.work_bytes, self.model.stream()), "p3d_clip_lift")
+        self._last_off = np.array([0, n], np.int64)
 
     def network_rows(self, n=None):
         """View of the network's normalised outputs [n, output_size] float32 that the last
@@ -500,6 +687,22 @@ class ClipLifter(_Lifter):
             p(self.dout_u) if unfiltered else None, p(self.dsrc_u) if unfiltered else None,
             p(self.dvar) if K else None, self.cwork_ptr, self.cwork_bytes, self.model.stream()), "p3d_clips_lift")
         self._clips = (S, N, vae is not None)
+        self._last_off = self._off
+
+    def skeleton(self, lengths=None):
+        """The rigid skeleton of the last lift_clip / lift_clips, from its device rows (dout, dsrc, the
+        clip offsets): p3d_skel_lengths and p3d_skel_pose, no model involved.  lengths: [16] or
+        [S, 16] bone lengths to use instead of each clip's own means.  Returns one dict per clip (one
+        for lift_clip): 'lengths' [16], 'n_used', 'quat' [n, 16, 4], 'euler' [n, 16, 3] (Z, X, Y
+        degrees), 'rigid' [n, 17, 3], 'root' [n, 3] -- see skeleton_rows."""
+        if self._last_off is None:
+            raise ValueError("no lift has run yet")
+        if self.model.output_size != 48:
+            raise ValueError("the skeleton needs the 17-joint model (48 outputs), this one predicts %d values"
+                             % self.model.output_size)
+        if self._skel is None:
+            self._skel = _SkeletonBuffers(self.torch, self.model.device)
+        return self._skel.run(self.dout, self.dsrc, self._last_off, lengths)
 
     def lift_clips(self, clips, smooth=True, vae=None, samples=None, eps=None, ctr=None, unfiltered=False):
         """A list of clips, each [n_s, 36] raw keypoints in position order (sum n_s <= max_frames), in

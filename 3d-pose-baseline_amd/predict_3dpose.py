@@ -78,6 +78,10 @@ def build_parser():
     p.add_argument("--max_batch", type=int, default=8192,
                    help="rows the device workspaces hold (evaluation submits up to this many rows per "
                         "launch); front ends stepping single frames can pass their batch size")
+    p.add_argument("--export_bvh", action='store_true', default=False,
+                   help="openpose front ends: also write skeleton.bvh (constant bone lengths, per-bone "
+                        "rotations) beside 3d_data.json")
+    p.add_argument("--bvh_fps", type=float, default=30.0, help="--export_bvh: frames per second of the BVH file")
     p.add_argument("--sample_dir", type=str, default="",
                    help="--sample: directory that receives samples.npz, the rows the reference would "
                         "draw (empty: not written)")

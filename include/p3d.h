@@ -613,6 +613,53 @@ int p3d_live_push(p3d_model* m, struct p3d_vae* v /* or NULL */, int32_t K, uint
                   int32_t cache_on_fail, int32_t smooth, double* xy_s, double* poses, int32_t* src,
                   float* ref_var /* or NULL */, void* work, int64_t work_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Lifted rows as a RIGID SKELETON: constant bone lengths per clip, one rotation per
+ * bone and frame, Euler angles for BVH, and the pose with the constant lengths.  `poses` [N, 96]
+ * float64 are rows as the clip, clips and live calls write them (32 joints, exported coordinates),
+ * S clips one after another under clip offsets as at the clips calls (host copy: validated, sizes
+ * the grids; device copy: read by the kernels, clamped into [0, N]; S = 1 with {0, N}: one clip).
+ * The 17 skeleton joints are H3.6M joints {0,1,2,3,6,7,8,12,13,14,15,17,18,19,25,26,27}, joint 0
+ * the hip, in skeleton coordinates (X, Y, Z) = (x, z, -y) (Y up); the 16 bones are the bones
+ * filter's (bone b from joint ja(b) to jb(b), parent bone pb(b)); the rest direction r_b is -X for
+ * the right hip / shoulder / elbow / wrist, +X for the left ones, -Y for knees and feet, +Y for
+ * spine, thorax, neck and head.  All arithmetic float64.  src [N] int32 is the clip calls' (row
+ * indices into the batch, -1: zeros) or NULL (every row carries its own pose).  The calls need no
+ * model, are asynchronous and capturable, and give the same bits on every run; a clip inside a
+ * batch carries the bits of the call on that clip alone.
+ *
+ * p3d_skel_lengths: lengths [S, 16] = per clip and bone the mean of |J[jb] - J[ja]| over the clip's
+ * frames n with src[n] == n whose 17 joints are all finite; n_used [S] int64 their number (0: 16
+ * zeros).  A workgroup owns p3d_skel_chunk() consecutive frames of one clip and a second launch
+ * folds a clip's partial sums in a fixed order (no atomics).  `work`: p3d_skel_workspace(N, S)
+ * bytes of device memory, 8-byte aligned.
+ *
+ * p3d_skel_pose, per frame and bone with d_b the bone's unit direction (a zero-length bone: r_b,
+ * and the identity for g_b; a row with src[n] < 0 counts as zeros whatever it holds):
+ *   quat  [N, 16, 4]  q_b = conj(g_pb) (x) g_b (w, x, y, z), g_b the shortest arc from r_b to d_b,
+ *                     normalize(1 + r.d, r x d), or (0, 0, 0, 1) where 1 + r.d < 1e-12; a hip bone: g_b.
+ *                     The twist about the bone is not determined by positions and stays the arc's;
+ *   euler [N, 16, 3]  (Z, X, Y) degrees of q_b with R = Rz Rx Ry -- BVH's Zrotation Xrotation Yrotation;
+ *   rigid [N, 17, 3]  P[0] = J[0], P[jb(b)] = P[ja(b)] + lengths[b] d_b;
+ *   root  [N, 3]      J[0].
+ * Each output may be NULL, not all.  lengths [S, 16] is device memory: p3d_skel_lengths' or the
+ * caller's own (a known actor, a live stream).  A non-finite joint gives what the arithmetic gives.
+ *
+ * P3D_ERR_ARG ("p3d_skel_lengths: ..." / "p3d_skel_pose: ...") without touching the GPU: a null
+ * poses, lengths, n_used or offsets; all four outputs null; N or S outside 1 <= S <= N <= 2^20;
+ * offsets that do not start at 0, decrease, hold an empty clip or do not end at N; a null, short
+ * or misaligned (8 bytes) workspace.
+ * ------------------------------------------------------------------------------------- */
+int32_t p3d_skel_chunk(void);
+int64_t p3d_skel_workspace(int64_t N, int64_t S);
+int p3d_skel_lengths(const double* poses, const int32_t* src /* or NULL */, const int64_t* clip_off_host,
+                     const int64_t* clip_off_dev, int64_t S, int64_t N, double* lengths /* [S, 16] */,
+                     int64_t* n_used /* [S] */, void* work, int64_t work_bytes, void* stream);
+int p3d_skel_pose(const double* poses, const int32_t* src /* or NULL */, const int64_t* clip_off_host,
+                  const int64_t* clip_off_dev, int64_t S, int64_t N, const double* lengths /* [S, 16], device */,
+                  double* quat, double* euler, double* rigid, double* root /* each may be NULL, not all */,
+                  void* stream);
+
 /* np.mean / np.std (population) over axis 0 of x [F, D], D <= 256 -- the statistics of
  * src/data_utils.py:210-211 (normalization_stats).  Deterministic two-level column sums;
  * `work` must hold p3d_moments_workspace(F, D) bytes of device memory. */
