@@ -149,6 +149,16 @@ SIGNATURES = [
                                    c_void_p, c_int64, c_void_p]),
     ("p3d_skel_pose", c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("p3d_clips_resample_workspace", c_int64, [c_int64, c_int64, c_int32]),
+    ("p3d_clips_resample", c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p,
+                                     c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                     c_void_p]),
+    ("p3d_clips_lift_resampled_workspace", c_int64, [c_int64, c_int64, c_int32, c_int32, c_int32, c_int32]),
+    ("p3d_clips_lift_resampled", c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_uint64, c_int64,
+                                           c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32,
+                                           c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
+                                           c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     ("p3d_moments_workspace", c_int64, [c_int64, c_int32]),
     ("p3d_moments", c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     ("p3d_crc32c", c_uint32, [c_void_p, c_int64, c_uint32]),

@@ -24,6 +24,7 @@
 #include "p3d_clips.h"
 #include "p3d_live.h"
 #include "p3d_skel.h"
+#include "p3d_spline.h"
 #include "p3d_serve.h"
 #include "p3d_serve6.h"
 #include "p3d_serve_plan.h"
@@ -66,5 +67,7 @@
 #include "p3d_live_host.h"
 // Lifted rows as a rigid skeleton: bone lengths, rotations, rigid pose (kernels in p3d_skel.h)
 #include "p3d_skel_host.h"
+// Spline-resampled clips: the fit, the samples and the lift over them (kernels in p3d_spline.h)
+#include "p3d_spline_host.h"
 
 #include "p3d_dp.h"

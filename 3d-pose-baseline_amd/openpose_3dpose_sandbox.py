@@ -12,9 +12,15 @@ re-anchors the axes (:366-383) and replaces failed frames with the last good one
 (``predict_3dpose.load_data``; ``--use_sh`` for the Stacked Hourglass detections the reference's
 sandbox normalises with).
 
-Not built (they need scipy / matplotlib and are not hot paths): ``--interpolation``
-(UnivariateSpline resampling, :240-291), the curve and pose plots, ``--write_gif``.  The driver
-refuses those flags.  ``--out_dir`` (build-specific) names the export directory.
+Not built (they need matplotlib and are not hot paths): the curve and pose plots, ``--write_gif``.
+The reference's ``--interpolation --multiplier 1/R`` (UnivariateSpline resampling, :240-291) is built
+as ``--spline_resample R`` (build-specific, R a whole number 1..16: R output frames per input frame,
+the reference's default multiplier 0.1 is R = 10): every smoothed 2D track is fitted with the
+reference's cubic smoothing spline on the GPU and sampled R times per frame inside the same
+``p3d_clips_lift_resampled`` call, and the export's frames are numbered 0 .. R m - 1 as the reference
+renumbers them.  ``--interpolation`` itself still exits, pointing at
+``--spline_resample`` (multipliers that are not 1/R garble the reference's own reshaping).
+``--out_dir`` (build-specific) names the export directory.
 
 Build-specific, all in ONE ``p3d_clips_lift``: ``--clips_root DIR`` lifts every clip under DIR (each
 immediate subdirectory with frame files, exported to ``<out_dir>/<clip name>/``);
@@ -54,6 +60,9 @@ def build_parser():
     p.add_argument("--filter_samples", type=int, default=None, help="average K posterior samples per frame (1 .. 64)")
     p.add_argument("--export_unfiltered", action="store_true", default=False,
                    help="also write 3d_data_unfiltered.json (needs --vae_filter)")
+    p.add_argument("--spline_resample", type=int, default=None,
+                   help="R output frames per input frame through the reference's smoothing spline "
+                        "(its --interpolation --multiplier 1/R), 1..16; every clip needs 4 frames")
     p.add_argument("--latent_dim", type=int, default=24, help="VAE latent dimension")
     p.add_argument("--enc_dim", type=int, nargs="+", default=[40, 32], help="VAE encoder dimension")
     p.add_argument("--dec_dim", type=int, nargs="+", default=[32, 40], help="VAE decoder dimension")
@@ -83,7 +92,7 @@ def write_bvh(flags, out_dir, frame_numbers, sk):
 
 
 def run_clips(flags):
-    """--clips_root / --vae_filter: one p3d_clips_lift over every clip."""
+    """--clips_root / --vae_filter / --spline_resample: one p3d_clips_lift (p3d_clips_lift_resampled) over every clip."""
     if flags.clips_root:
         names, numbers, clips = of.read_clips(flags.clips_root)
     else:
@@ -101,7 +110,9 @@ def run_clips(flags):
         vae = load_filter(flags, model) if flags.vae_filter else None
         logger.info("lifting %d clips, %d frames", len(clips), sum(len(c) for c in clips))
         results = lifter.lift_clips(clips, smooth=smooth, vae=vae, samples=flags.filter_samples,
-                                    unfiltered=flags.export_unfiltered)
+                                    unfiltered=flags.export_unfiltered, resample=flags.spline_resample)
+        if flags.spline_resample is not None:                 # the resampled frames, renumbered from 0 (:283-284)
+            numbers = [np.arange(len(r["poses"]), dtype=np.int64) for r in results]
         skeletons = lifter.skeleton() if flags.export_bvh else None
         if vae is not None:
             vae.close()
@@ -125,16 +136,19 @@ def run_clips(flags):
 
 def run(flags):
     if flags.interpolation:
-        raise SystemExit("--interpolation (UnivariateSpline resampling) is not part of this build")
+        raise SystemExit("--interpolation (UnivariateSpline resampling) is not part of this build: "
+                         "--spline_resample R is its --multiplier 1/R")
     if flags.write_gif:
         raise SystemExit("--write_gif (matplotlib pose plots) is not part of this build")
+    if flags.spline_resample is not None and not 1 <= flags.spline_resample <= 16:
+        raise SystemExit("--spline_resample must be in 1..16")
     logging.basicConfig(level={0: logging.ERROR, 1: logging.WARNING, 2: logging.INFO,
                                3: logging.DEBUG}.get(flags.verbose, logging.INFO))
     if (flags.filter_samples is not None or flags.export_unfiltered) and not flags.vae_filter:
         raise SystemExit("--filter_samples and --export_unfiltered need --vae_filter")
     if flags.export_bvh and flags.predict_14:
         raise SystemExit("--export_bvh needs the 17-joint model: the skeleton's bones are not defined for --predict_14")
-    if flags.clips_root or flags.vae_filter:
+    if flags.clips_root or flags.vae_filter or flags.spline_resample is not None:
         return run_clips(flags)
     logger.info("start reading json files")
     frame_numbers, xy = of.read_openpose_json(flags.pose_estimation_json)

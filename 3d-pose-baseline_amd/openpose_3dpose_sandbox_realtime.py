@@ -23,7 +23,9 @@ written) is tried again at the next poll; a gap in the frame numbers is waited f
 still there at the idle exit, refused like the clip driver refuses it.
 
 Not built: the pose plots and the ``cv2`` window of the reference (matplotlib / OpenCV, not hot
-paths).
+paths).  ``--interpolation`` and the clip driver's ``--spline_resample`` are refused: a smoothing spline
+is fitted over the whole clip, every sample depends on frames that have not arrived yet, so it is not
+causal and has no place in a stream.
 """
 from __future__ import annotations
 
@@ -121,8 +123,9 @@ def run_stream(flags, lifter, on_rows=None, clock=time.monotonic, sleep=time.sle
 
 
 def run(flags):
-    if flags.interpolation:
-        raise SystemExit("--interpolation (UnivariateSpline resampling) is not part of this build")
+    if flags.interpolation or flags.spline_resample is not None:
+        raise SystemExit("--interpolation / --spline_resample (UnivariateSpline resampling) fit a spline over the whole "
+                         "clip, which is not causal: use openpose_3dpose_sandbox.py --spline_resample R on the recorded clip")
     if flags.write_gif:
         raise SystemExit("--write_gif (matplotlib pose plots) is not part of this build")
     if flags.clips_root or flags.export_unfiltered:

@@ -15,8 +15,8 @@ a host-side index shuffle of the OpenPose JSON values (as in the reference).
 ``p3d_clip_lift``: the median smoothing and the hold of dropped joints, the mapping, the forward
 in tiles of ``max_batch`` rows, the axis swap / flip / spine offset and ``--cache_on_fail``, from
 pinned rows in to pinned rows out.  ``read_openpose_json`` parses the frame files and
-``export_maya`` writes ``3d_data.json`` / ``2d_data.json``.  The plots, ``--interpolation`` and
-``--write_gif`` stay out of scope.
+``export_maya`` writes ``3d_data.json`` / ``2d_data.json``.  The plots and ``--write_gif`` stay out
+of scope; ``--interpolation``'s spline resampling is ``lift_clips(resample=R)``.
 
 ``ClipLifter.lift_clips`` lifts a BATCH of clips in one ``p3d_clips_lift`` (every clip the bits of
 ``lift_clip`` on it alone), optionally with the temporal VAE filter (``models.VAE``, the filter
@@ -576,6 +576,8 @@ class ClipLifter(_Lifter):
         self.cwork, self.cwork_ptr, self.cwork_bytes = None, 0, 0
         self.hout_u, self.hsrc_u, self.dout_u, self.dsrc_u, self.hvar, self.dvar = (None,) * 6
         self._last_off, self._skel = None, None              # the last lift's clip offsets; skeleton()'s buffers
+        self._last_rows = None                               # the last lift's device rows where not dout / dsrc (resampled)
+        self._rs = None                                      # the resampled lift's buffers (_resample_buffers)
 
     def lift_device(self, n, smooth=True):
         """p3d_clip_lift of the first n rows of self.din into self.dxy / dout / dsrc (current stream)."""
@@ -585,7 +587,7 @@ class ClipLifter(_Lifter):
             self.model._h, p(self.din), n, int(bool(smooth)), p(self.m2), p(self.s2), p(self.u2), self.u2.numel(),
             p(self.m3), p(self.s3), p(self.u3), self.u3.numel(), 96, int(self.cache_on_fail), p(self.dxy),
             p(self.dout), p(self.dsrc), self.work_ptr, self.work_bytes, self.model.stream()), "p3d_clip_lift")
-        self._last_off = np.array([0, n], np.int64)
+        self._last_off, self._last_rows = np.array([0, n], np.int64), None
 
     def network_rows(self, n=None):
         """View of the network's normalised outputs [n, output_size] float32 that the last
@@ -687,7 +689,81 @@ class ClipLifter(_Lifter):
             p(self.dout_u) if unfiltered else None, p(self.dsrc_u) if unfiltered else None,
             p(self.dvar) if K else None, self.cwork_ptr, self.cwork_bytes, self.model.stream()), "p3d_clips_lift")
         self._clips = (S, N, vae is not None)
-        self._last_off = self._off
+        self._last_off, self._last_rows = self._off, None
+
+    # ------------------------------------------------------------------ spline-resampled clips
+    def _resample_buffers(self, S, N, R, filtered, unfiltered, variance):
+        """The resampled call's workspace and its R N output rows, grown on demand (as _clips_buffers: a
+        captured graph holds the addresses)."""
+        import _p3d
+        torch, dev, rows = self.torch, self.model.device, R * N
+        need = int(_p3d.lib().p3d_clips_lift_resampled_workspace(N, S, R, self.model.input_size, self.model.output_size,
+                                                                 int(filtered)))
+        rs = self._rs or dict(rows=0, S=0, work_bytes=0, unf=False, var=False)
+        with torch.cuda.device(dev):
+            if need > rs["work_bytes"]:
+                rs["work"], rs["work_ptr"] = _aligned_workspace(torch, need, dev)
+                rs["work_bytes"] = need
+            if rows > rs["rows"] or (unfiltered and not rs["unf"]) or (variance and not rs["var"]):
+                rows = max(rows, rs["rows"])
+                f64, i32 = torch.float64, torch.int32
+                pair = lambda shape, dt: (torch.empty(shape, dtype=dt, pin_memory=True),   # noqa: E731
+                                          torch.empty(shape, dtype=dt, device=dev))
+                rs["hxy"], rs["dxy"] = pair((rows, 36), f64)
+                rs["hout"], rs["dout"] = pair((rows, 96), f64)
+                rs["hsrc"], rs["dsrc"] = pair((rows,), i32)
+                if unfiltered or rs["unf"]:
+                    rs["hout_u"], rs["dout_u"] = pair((rows, 96), f64)
+                    rs["hsrc_u"], rs["dsrc_u"] = pair((rows,), i32)
+                    rs["unf"] = True
+                if variance or rs["var"]:
+                    rs["hvar"], rs["dvar"] = pair((rows, self.model.output_size), torch.float32)
+                    rs["var"] = True
+                rs["rows"] = rows
+            if S > rs["S"]:
+                rs["hinfo"] = torch.empty((S, 36, 5), dtype=torch.int32, pin_memory=True)
+                rs["dinfo"] = torch.empty((S, 36, 5), dtype=torch.int32, device=dev)
+                rs["doff"] = torch.empty((S + 1,), dtype=torch.int64, device=dev)
+                rs["S"] = S
+        self._rs = rs
+        return rs
+
+    def lift_clips_resampled_device(self, resample, smooth=True, vae=None, samples=None, eps=None, ctr=0, eps_row0=0,
+                                    unfiltered=False):
+        """ONE p3d_clips_lift_resampled of the rows self.din[:N] under the offsets of the last set_offsets:
+        smoothing into self.dxy, the spline resampling (the reference's --interpolation --multiplier
+        1 / resample) into the R N rows of self._rs['dxy'], and the lift of those rows into
+        self._rs['dout'] / ['dsrc'] (['dout_u'] / ['dsrc_u'], ['dvar']); ['dinfo'] [S, 36, 5] is the
+        fits' record and ['doff'] the resampled clips' offsets.  On the current stream; capturable.
+        eps rows count over the R N resampled rows."""
+        import _p3d
+        if self._off is None:
+            raise ValueError("set_offsets first")
+        R = int(resample)
+        if R != resample or not 1 <= R <= 16:
+            raise ValueError("resample must be a whole number in 1..16 (the reference's multiplier 1 / resample)")
+        S, N = self._off.shape[0] - 1, int(self._off[-1])
+        K = 0
+        if vae is None:
+            if samples is not None or eps is not None or unfiltered:
+                raise ValueError("samples, eps and unfiltered need a filter (vae=...)")
+        else:
+            K = _check_filter(vae, samples, self.model.output_size, "lift_clips")
+            want = (K, R * N, vae.latent_dim) if K else (R * N, vae.latent_dim)
+            if eps is not None and (tuple(eps.shape) != want or eps.dtype != self.torch.float32 or not eps.is_cuda
+                                    or not eps.is_contiguous()):
+                raise ValueError("eps: expected a contiguous float32 device tensor %s" % (want,))
+        rs = self._resample_buffers(S, N, R, vae is not None, unfiltered, K > 0)
+        p = _p3d.ptr
+        _p3d.check(_p3d.lib().p3d_clips_lift_resampled(
+            self.model._h, None if vae is None else vae._h, K, p(eps), int(ctr), int(eps_row0),
+            p(self.din), self._off.ctypes.data, p(self.doff), S, N, int(bool(smooth)),
+            p(self.m2), p(self.s2), p(self.u2), self.u2.numel(), p(self.m3), p(self.s3), p(self.u3), self.u3.numel(), 96,
+            int(self.cache_on_fail), p(self.dxy), p(rs["dout"]), p(rs["dsrc"]),
+            p(rs["dout_u"]) if unfiltered else None, p(rs["dsrc_u"]) if unfiltered else None,
+            p(rs["dvar"]) if K else None, R, p(rs["dxy"]), p(rs["doff"]), p(rs["dinfo"]),
+            rs["work_ptr"], rs["work_bytes"], self.model.stream()), "p3d_clips_lift_resampled")
+        self._last_off, self._last_rows = self._off * R, (rs["dout"], rs["dsrc"])
 
     def skeleton(self, lengths=None):
         """The rigid skeleton of the last lift_clip / lift_clips, from its device rows (dout, dsrc, the
@@ -702,9 +778,11 @@ class ClipLifter(_Lifter):
                              % self.model.output_size)
         if self._skel is None:
             self._skel = _SkeletonBuffers(self.torch, self.model.device)
-        return self._skel.run(self.dout, self.dsrc, self._last_off, lengths)
+        dout, dsrc = self._last_rows or (self.dout, self.dsrc)
+        return self._skel.run(dout, dsrc, self._last_off, lengths)
 
-    def lift_clips(self, clips, smooth=True, vae=None, samples=None, eps=None, ctr=None, unfiltered=False):
+    def lift_clips(self, clips, smooth=True, vae=None, samples=None, eps=None, ctr=None, unfiltered=False,
+                   resample=None):
         """A list of clips, each [n_s, 36] raw keypoints in position order (sum n_s <= max_frames), in
         ONE p3d_clips_lift: every clip is smoothed, lifted and post-processed as lift_clip does it
         alone, bit for bit.  vae: a models.VAE sequence filter (in = seq_len * out) that refines the
@@ -713,7 +791,15 @@ class ClipLifter(_Lifter):
         library's stream at counter ctr (None: a fresh one, as filter_sequences).  Returns one dict
         per clip: 'poses' [n_s, 96], 'xy_s' [n_s, 36], 'src' [n_s] (positions inside the clip, -1
         zeros), with unfiltered=True 'poses_unfiltered' / 'src_unfiltered' (the lift without the
-        filter) and with samples 'ref_var' [n_s, out] float32 (the draws' variance)."""
+        filter) and with samples 'ref_var' [n_s, out] float32 (the draws' variance).
+
+        resample=R (1..16): the reference's --interpolation --multiplier 1/R in the same call
+        (p3d_clips_lift_resampled): every smoothed track is fitted with the reference's
+        cubic smoothing spline and sampled R times per frame, and the R n_s resampled rows are what the
+        lifter, the filter and the post-processing see.  Every clip needs at least 4 frames.  Each
+        result then holds R n_s rows -- 'poses', 'xy_s' (the resampled rows), 'src', the optional ones --
+        plus 'spline_info' [36, 5] int32 (per track: knots after the first and the second fit, FITPACK's
+        ier of each, the p iterations); eps rows count over the resampled rows."""
         rows = [np.asarray(c, np.float64) for c in clips]
         if not rows:
             raise ValueError("expected at least one clip")
@@ -726,6 +812,16 @@ class ClipLifter(_Lifter):
         N = int(off[-1])
         if N > self.max_frames:
             raise ValueError("%d frames in all, max_frames is %d" % (N, self.max_frames))
+        R = 1
+        if resample is not None:
+            R = int(resample)
+            if R != resample or not 1 <= R <= 16:
+                raise ValueError("resample must be a whole number in 1..16 (the reference's multiplier 1 / resample)")
+            if min(r.shape[0] for r in rows) < 4:
+                raise ValueError("need more frames, min 4 frames for a cubic spline")
+            if R * N > 1 << 20:
+                raise ValueError("%d resampled rows in all, at most 2^20" % (R * N))
+        N, N_in, off_in, off = R * N, N, off, off * R        # (rows and offsets of the results)
         torch, K = self.torch, None
         if vae is not None:
             vae._seq_len()
@@ -737,35 +833,48 @@ class ClipLifter(_Lifter):
             if ctr is None:
                 ctr = vae._calls + 1
                 vae._calls += K or 1
-        np.concatenate(rows, out=self.hin.numpy()[:N])
+        np.concatenate(rows, out=self.hin.numpy()[:N_in])
         with torch.cuda.device(self.model.device):
-            self.set_offsets(off)
-            self.din[:N].copy_(self.hin[:N], non_blocking=True)
-            self.lift_clips_device(smooth, vae, samples, eps, ctr or 0, 0, unfiltered)
-            pairs = [(self.hxy, self.dxy), (self.hout, self.dout), (self.hsrc, self.dsrc)]
-            if unfiltered:
-                pairs += [(self.hout_u, self.dout_u), (self.hsrc_u, self.dsrc_u)]
-            if K:
-                pairs.append((self.hvar, self.dvar))
-            for h, d in pairs:
-                h[:N].copy_(d[:N], non_blocking=True)
+            self.set_offsets(off_in)
+            self.din[:N_in].copy_(self.hin[:N_in], non_blocking=True)
+            if resample is None:
+                self.lift_clips_device(smooth, vae, samples, eps, ctr or 0, 0, unfiltered)
+                b = dict(hxy=self.hxy, dxy=self.dxy, hout=self.hout, dout=self.dout, hsrc=self.hsrc, dsrc=self.dsrc,
+                         hout_u=self.hout_u, dout_u=self.dout_u, hsrc_u=self.hsrc_u, dsrc_u=self.dsrc_u,
+                         hvar=self.hvar, dvar=self.dvar)
+            else:
+                self.lift_clips_resampled_device(R, smooth, vae, samples, eps, ctr or 0, 0, unfiltered)
+                b = self._rs
+                b["hinfo"][:len(rows)].copy_(b["dinfo"][:len(rows)], non_blocking=True)
+            keys = ["xy", "out", "src"] + (["out_u", "src_u"] if unfiltered else []) + (["var"] if K else [])
+            for k in keys:
+                b["h" + k][:N].copy_(b["d" + k][:N], non_blocking=True)
             torch.cuda.current_stream(self.model.device).synchronize()
         self.model.check_errors()
         first = np.repeat(off[:-1], np.diff(off))            # every row's clip start: 'src' counts from it (-1 stays)
         local = lambda t: np.where(t.numpy()[:N] >= 0, t.numpy()[:N] - first, -1).astype(np.int32)   # noqa: E731
-        views = [("poses", self.hout.numpy()), ("xy_s", self.hxy.numpy()), ("src", local(self.hsrc))]
+        views = [("poses", b["hout"].numpy()), ("xy_s", b["hxy"].numpy()), ("src", local(b["hsrc"]))]
         if unfiltered:
-            views += [("poses_unfiltered", self.hout_u.numpy()), ("src_unfiltered", local(self.hsrc_u))]
+            views += [("poses_unfiltered", b["hout_u"].numpy()), ("src_unfiltered", local(b["hsrc_u"]))]
         if K:
-            views.append(("ref_var", self.hvar.numpy()))
-        return self._results(off.tolist(), views)
+            views.append(("ref_var", b["hvar"].numpy()))
+        res = self._results(off.tolist(), views)
+        if resample is not None:
+            for s, r in enumerate(res):
+                r["spline_info"] = b["hinfo"].numpy()[s].copy()
+        return res
 
-    def lift_clip(self, xy, smooth=True):
+    def lift_clip(self, xy, smooth=True, resample=None):
         """xy [N <= max_frames, 36] raw keypoints in position order -> (poses [N, 96] float64 mm,
-        xy_s [N, 36] float64, src [N] int32: the position each exported pose came from, -1 zeros)."""
+        xy_s [N, 36] float64, src [N] int32: the position each exported pose came from, -1 zeros).
+        resample=R: the clip through lift_clips(resample=R) as a batch of one -> (poses [R N, 96], xy_s
+        [R N, 36] the resampled rows, src [R N], spline_info [36, 5])."""
         xy = np.asarray(xy, np.float64)
         if xy.ndim != 2 or xy.shape[1] != 36 or not 1 <= xy.shape[0] <= self.max_frames:
             raise ValueError("expected [1..%d, 36] keypoint rows, got %s" % (self.max_frames, xy.shape))
+        if resample is not None:
+            r = self.lift_clips([xy], smooth, resample=resample)[0]
+            return r["poses"], r["xy_s"], r["src"], r["spline_info"]
         n = xy.shape[0]
         if smooth and 2 <= n <= 8:
             raise ValueError("need more frames, min 9 frames for smoothing")

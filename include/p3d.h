@@ -660,6 +660,55 @@ int p3d_skel_pose(const double* poses, const int32_t* src /* or NULL */, const i
                   double* quat, double* euler, double* rigid, double* root /* each may be NULL, not all */,
                   void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * SPLINE-RESAMPLED clips (the reference's --interpolation --multiplier 1/R,
+ * src/openpose_3dpose_sandbox.py:240-291).  Each of a clip's 36 smoothed tracks y over the frames
+ * 0 .. m - 1 is fitted as scipy's UnivariateSpline(frame, y, k=3) followed by
+ * set_smoothing_factor((max(y) - min(y)) * 125) fits it: FITPACK's curfit with s = m, then again with
+ * iopt = 1 CONTINUING from the first call's knots and saved state (not a fresh fit).  The spline is
+ * sampled at j * (1.0 / R), j = 0 .. R m - 1 (the last R - 1 positions extrapolate the last piece),
+ * and the samples, renumbered from 0, are the clip the lifter sees.  All float64, no contraction,
+ * + - * / sqrt fabs only, one fixed operation order: the same bits on every run, and a clip inside a
+ * batch carries the bits of the call on that clip alone.  A non-finite sample follows the arithmetic.
+ *
+ * p3d_clips_resample: xy_s [N, 36] (p3d_clips_prepare's) under clip offsets as at the clips calls ->
+ *   xy_r [R N, 36]; x [R N, U2] float32, the bits of p3d_clips_prepare(xy_r, smooth = 0);
+ *   off_out_dev [S + 1] = R * off (device, clamped as read); info [S, 36, 5] int32 or NULL: per curve
+ *   n after stage 1, n after stage 2, FITPACK's ier of either stage (-2 the least-squares polynomial,
+ *   -1 the interpolating spline, 0 the smoothing spline, 2 / 3 the p search gave up or ran out of its
+ *   20 iterations: the fit stands as FITPACK returns it; 5, ours: no knot interval could take a knot),
+ *   and the p iterations of stage 2.
+ *   `work`: p3d_clips_resample_workspace(N, S, R) bytes of device memory, 8-byte aligned:
+ *   t f64 [36 (N + 4 S)] | c f64 [36 (N + 4 S)] | info i32 [S, 36, 5] | the state of curves too long for
+ *   LDS, every area 256-byte aligned; the curve of clip s (rows lo .., m frames) and column col keeps
+ *   its n knots and coefficients at 36 (lo + 4 s) + col (m + 4) of t and c.
+ * p3d_clips_lift_resampled: p3d_clips_lift with the resampling between prepare and the forward; xy_s
+ *   [N, 36] stays the smoothed rows, xy_r [R N, 36], poses [R N, 96], src [R N] (and the unfiltered
+ *   outputs, ref_var [R N, U3], eps [R N, latent]) are rows of the resampled clips, whose forward
+ *   tiles start again at every clip's first resampled row and whose filter sequences are off_out_dev:
+ *   p3d_clips_lift on the xy_r clips with smooth = 0, bit for bit.
+ * P3D_ERR_ARG without touching the GPU, the message starting with the call's name: a null argument;
+ * R outside 1 .. 16; a clip under 4 frames (FITPACK needs m > k) or over 65,536; R N > 2^20; what the
+ * clips calls refuse of N, S and the offsets; a null, short or misaligned workspace (8 bytes;
+ * p3d_clips_lift_resampled: 256); aliased xy / xy_s / xy_r; and at p3d_clips_lift_resampled everything
+ * p3d_clips_lift refuses.
+ * ------------------------------------------------------------------------------------- */
+int64_t p3d_clips_resample_workspace(int64_t N, int64_t S, int32_t R);
+int p3d_clips_resample(const double* xy_s, const int64_t* clip_off_host, const int64_t* clip_off_dev, int64_t S,
+                       int64_t N, int32_t R, const double* mean2, const double* std2, const int32_t* use2, int32_t U2,
+                       float* x, double* xy_r, int64_t* off_out_dev, int32_t* info /* or NULL */, void* work,
+                       int64_t work_bytes, void* stream);
+int64_t p3d_clips_lift_resampled_workspace(int64_t N, int64_t S, int32_t R, int32_t U2, int32_t U3, int32_t with_filter);
+int p3d_clips_lift_resampled(p3d_model* m, struct p3d_vae* v /* or NULL */, int32_t K, const float* eps, uint64_t ctr,
+                             int64_t eps_row0, const double* xy, const int64_t* clip_off_host,
+                             const int64_t* clip_off_dev, int64_t S, int64_t N, int32_t smooth, const double* mean2,
+                             const double* std2, const int32_t* use2, int32_t U2, const double* mean3,
+                             const double* std3, const int32_t* use3, int32_t U3, int32_t D3, int32_t cache_on_fail,
+                             double* xy_s, double* poses, int32_t* src, double* poses_unfiltered /* or NULL */,
+                             int32_t* src_unfiltered /* or NULL */, float* ref_var /* or NULL */, int32_t R,
+                             double* xy_r, int64_t* off_out_dev, int32_t* info /* or NULL */, void* work,
+                             int64_t work_bytes, void* stream);
+
 /* np.mean / np.std (population) over axis 0 of x [F, D], D <= 256 -- the statistics of
  * src/data_utils.py:210-211 (normalization_stats).  Deterministic two-level column sums;
  * `work` must hold p3d_moments_workspace(F, D) bytes of device memory. */
