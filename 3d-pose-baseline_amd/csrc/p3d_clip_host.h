@@ -2,8 +2,9 @@
 // p3d_clip.h; src/openpose_3dpose_sandbox.py:140-227, 317-417) and the stage that the three lift
 // calls share (p3d_clip_lift here, p3d_clips_lift in p3d_clips_host.h, p3d_live_push in
 // p3d_live_host.h): the statistics' way into the kernel arguments, the workspace layout, the model
-// check, the forward tiles and the filter stage.  Included by p3d.hip behind p3d_vae_host.h (the
-// filter calls) and p3d_forward_host.h (forward_impl).
+// check, the forward tiles and the filter stage; and the checked arguments of the two batched calls
+// (p3d_clips_lift, p3d_clips_lift_resampled in p3d_spline_host.h).  Included by p3d.hip behind
+// p3d_vae_host.h (the filter calls) and p3d_forward_host.h (forward_impl).
 #pragma once
 
 namespace {
@@ -56,6 +57,42 @@ int lift_check_filter(const char* what, const p3d_vae* v, int32_t U3) {
   if (f == VAE_SEQ_BONES) return fail(P3D_ERR_ARG, std::string(what) + ": a bones filter has no sequence form");
   if (f != VAE_SEQ_OK)
     return fail(P3D_ERR_ARG, std::string(what) + ": the filter must be a sequence filter with out == U3 and in == seq_len * U3");
+  return P3D_OK;
+}
+
+// the two batched lift calls (p3d_clips_lift, p3d_clips_lift_resampled): the filter's arguments and the
+// outputs that need one, as the entry points take them
+struct LiftFilter {
+  p3d_vae* v; int32_t K; const float* eps; uint64_t ctr; int64_t eps_row0;
+  double* poses_unfiltered; int32_t* src_unfiltered; float* ref_var;
+};
+
+// the checked arguments: the model, the statistics, U2 / U3 / D3, the alias, the filter block.
+// null_arg: one of the call's own pointers is null; alias: the call's own alias fault, null: none
+int lift_batch_check(const char* what, const p3d_model* m, const LiftFilter& f, bool null_arg, int32_t U2, int32_t U3,
+                     int32_t D3, const char* alias) {
+  const std::string w(what);
+  if (!m) return fail(P3D_ERR_ARG, w + ": null model");
+  if (null_arg) return fail(P3D_ERR_ARG, w + ": null argument");
+  if (int rc = lift_check_model(what, m, U2, U3)) return rc;
+  if (U2 < 1 || U2 > 64 || U3 < 1 || U3 > P3D_CLIP_D3) return fail(P3D_ERR_ARG, w + ": U2 must be in 1..64, U3 in 1..96");
+  if (D3 != P3D_CLIP_D3) return fail(P3D_ERR_ARG, w + ": D3 must be 96 (32 joints)");
+  if (alias) return fail(P3D_ERR_ARG, w + ": " + alias);
+  if (!f.v) {
+    if (f.ref_var || f.poses_unfiltered || f.src_unfiltered)
+      return fail(P3D_ERR_ARG, w + ": ref_var and the unfiltered outputs need a filter");
+    return P3D_OK;
+  }
+  if (int rc = lift_check_filter(what, f.v, U3)) return rc;
+  if (f.K < 0 || f.K > P3D_VAE_MC_MAX_K)
+    return fail(P3D_ERR_ARG, w + ": K must be in 1 .. " + std::to_string(P3D_VAE_MC_MAX_K) + " (0: one draw)");
+  if (f.K >= 1 && f.ctr == P3D_CTR_GLOBAL_STEP)
+    return fail(P3D_ERR_ARG, w + ": draw k uses the counter ctr + k (ctr may not be P3D_CTR_GLOBAL_STEP)");
+  if (f.ref_var && f.K < 1) return fail(P3D_ERR_ARG, w + ": ref_var needs K >= 1");
+  if (f.src_unfiltered && !f.poses_unfiltered) return fail(P3D_ERR_ARG, w + ": src_unfiltered needs poses_unfiltered");
+  if (f.eps_row0 < 0) return fail(P3D_ERR_ARG, w + ": eps_row0 must be >= 0");
+  if ((uintptr_t)f.eps % 16 != 0 || (uintptr_t)f.ref_var % 16 != 0)
+    return fail(P3D_ERR_ARG, w + ": eps and ref_var must be 16-byte aligned");
   return P3D_OK;
 }
 

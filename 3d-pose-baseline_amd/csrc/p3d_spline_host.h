@@ -1,9 +1,9 @@
 // p3d_spline_host.h -- the host side of the spline resampling (include/p3d.h: p3d_clips_resample*,
-// p3d_clips_lift_resampled*; kernels in p3d_spline.h): the checks that answer before
-// the GPU is touched, the two launches, and the clips lift with the resampling between prepare and
-// the forward.  Included by p3d.hip behind p3d_clips_host.h (the clips' checks and launches) and
-// p3d_clip_host.h (the stage the lift calls share: LiftLayout, lift_check_model, lift_forward,
-// lift_filter_run).
+// p3d_clips_lift_resampled*; kernels in p3d_spline.h): the spline's own checks (R, the
+// rows, the frames per clip, the LDS plan), the two launches, and the clips lift with the resampling
+// between prepare and the forward.  Included by p3d.hip behind p3d_clips_host.h (the check of the
+// offsets, the clips' launches, and the checked arguments and the run tail the two batched lift calls
+// share) and p3d_clip_host.h (LiftLayout, the statistics).
 //
 // p3d_clips_resample's workspace (bytes, every area 256-aligned):
 //   t f64 [36 (N + 4 S)] | c f64 [36 (N + 4 S)] | info i32 [S, 36, 5] | state f64 [36 (N + 4 S) * 24]
@@ -34,7 +34,7 @@ struct SplinePlan {
   int64_t max_m;
 };
 
-// what R and the offsets can be refused for, beyond clips_check
+// what R and the clips' lengths can be refused for, beyond clips_check_offsets (which has walked the offsets)
 int spline_check(const std::string& w, const int64_t* off_host, int64_t S, int64_t N, int32_t R, SplinePlan& sp) {
   if (R < 1 || R > P3D_SPL_MAX_R) return fail(P3D_ERR_ARG, w + ": R must be in 1.." + std::to_string(P3D_SPL_MAX_R));
   if ((int64_t)R * N > P3D_CLIP_MAX_N)
@@ -87,8 +87,8 @@ extern "C" int p3d_clips_resample(const double* xy_s, const int64_t* clip_off_ho
                                   int32_t* info, void* work, int64_t work_bytes, void* stream) {
   const std::string w("p3d_clips_resample");
   if (!xy_s || !mean2 || !std2 || !use2 || !x || !xy_r || !off_out_dev) return fail(P3D_ERR_ARG, w + ": null argument");
-  int64_t nch = 0;
-  if (int rc = skel_check_offsets(w, clip_off_host, clip_off_dev, S, N, nch)) return rc;
+  ClipsPlan pl;
+  if (int rc = clips_check_offsets(w, clip_off_host, clip_off_dev, S, N, 0, pl)) return rc;
   SplinePlan sp;
   if (int rc = spline_check(w, clip_off_host, S, N, R, sp)) return rc;
   if (U2 < 1 || U2 > 64) return fail(P3D_ERR_ARG, w + ": U2 must be in 1..64");
@@ -106,9 +106,9 @@ extern "C" int64_t p3d_clips_lift_resampled_workspace(int64_t N, int64_t S, int3
   return LiftLayout(nullptr, head, R * N, U2, U3, with_filter != 0).total;
 }
 
-// index, prepare (xy_s, the N smoothed rows), resample (xy_r, the model's R N input rows, off_out_dev), the
-// forward tiles starting again at every clip's first resampled row, the temporal filter over the
-// resampled clips, finish on xy_r -- p3d_clips_lift on the resampled clips with smooth = 0, bit for bit
+// index, prepare (xy_s, the N smoothed rows), resample (xy_r, the model's R N input rows, off_out_dev), index
+// over the R N rows, then lift_batch_tail on the resampled offsets and xy_r -- p3d_clips_lift on the resampled
+// clips with smooth = 0, bit for bit
 extern "C" int p3d_clips_lift_resampled(p3d_model* m, p3d_vae* v, int32_t K, const float* eps, uint64_t ctr,
                                         int64_t eps_row0, const double* xy, const int64_t* clip_off_host,
                                         const int64_t* clip_off_dev, int64_t S, int64_t N, int32_t smooth,
@@ -120,29 +120,12 @@ extern "C" int p3d_clips_lift_resampled(p3d_model* m, p3d_vae* v, int32_t K, con
                                         int64_t work_bytes, void* stream) {
   const char* what = "p3d_clips_lift_resampled";
   const std::string w(what);
-  if (!m) return fail(P3D_ERR_ARG, w + ": null model");
-  if (!xy || !mean2 || !std2 || !use2 || !mean3 || !std3 || !use3 || !xy_s || !poses || !xy_r || !off_out_dev)
-    return fail(P3D_ERR_ARG, w + ": null argument");
-  if (int rc = lift_check_model(what, m, U2, U3)) return rc;
-  if (U2 < 1 || U2 > 64 || U3 < 1 || U3 > P3D_CLIP_D3) return fail(P3D_ERR_ARG, w + ": U2 must be in 1..64, U3 in 1..96");
-  if (D3 != P3D_CLIP_D3) return fail(P3D_ERR_ARG, w + ": D3 must be 96 (32 joints)");
-  if ((const double*)xy_s == xy || xy_r == xy_s || (const double*)xy_r == xy)
-    return fail(P3D_ERR_ARG, w + ": xy, xy_s and xy_r must not alias");
-  if (!v) {
-    if (ref_var || poses_unfiltered || src_unfiltered)
-      return fail(P3D_ERR_ARG, w + ": ref_var and the unfiltered outputs need a filter");
-  } else {
-    if (int rc = lift_check_filter(what, v, U3)) return rc;
-    if (K < 0 || K > P3D_VAE_MC_MAX_K)
-      return fail(P3D_ERR_ARG, w + ": K must be in 1 .. " + std::to_string(P3D_VAE_MC_MAX_K) + " (0: one draw)");
-    if (K >= 1 && ctr == P3D_CTR_GLOBAL_STEP)
-      return fail(P3D_ERR_ARG, w + ": draw k uses the counter ctr + k (ctr may not be P3D_CTR_GLOBAL_STEP)");
-    if (ref_var && K < 1) return fail(P3D_ERR_ARG, w + ": ref_var needs K >= 1");
-    if (src_unfiltered && !poses_unfiltered) return fail(P3D_ERR_ARG, w + ": src_unfiltered needs poses_unfiltered");
-    if (eps_row0 < 0) return fail(P3D_ERR_ARG, w + ": eps_row0 must be >= 0");
-    if ((uintptr_t)eps % 16 != 0 || (uintptr_t)ref_var % 16 != 0)
-      return fail(P3D_ERR_ARG, w + ": eps and ref_var must be 16-byte aligned");
-  }
+  const LiftFilter f{v, K, eps, ctr, eps_row0, poses_unfiltered, src_unfiltered, ref_var};
+  if (int rc = lift_batch_check(what, m, f, !xy || !mean2 || !std2 || !use2 || !mean3 || !std3 || !use3 || !xy_s || !poses ||
+                                                !xy_r || !off_out_dev,
+                                U2, U3, D3, (const double*)xy_s == xy || xy_r == xy_s || (const double*)xy_r == xy
+                                                ? "xy, xy_s and xy_r must not alias" : nullptr))
+    return rc;
   ClipsPlan pl;
   if (int rc = clips_check(what, clip_off_host, clip_off_dev, S, N, smooth, work, work_bytes, pl)) return rc;
   SplinePlan sp;
@@ -158,18 +141,10 @@ extern "C" int p3d_clips_lift_resampled(p3d_model* m, p3d_vae* v, int32_t K, con
   if (int rc = clips_check(what, off_r.data(), off_out_dev, S, RN, 0, (char*)work + wb1 + sl.total, wb2, pr)) return rc;
   const LiftLayout l(work, wb1 + sl.total + wb2, RN, U2, U3, v != nullptr);
   const Stat2 s2{mean2, std2, use2, U2};
-  const Stat3 s3{mean3, std3, use3, U3, cache_on_fail};
   hipStream_t st = (hipStream_t)stream;
-  if (int rc = clips_index(pl, N, st)) return rc;
+  if (int rc = clips_index(pl.g, N, st)) return rc;
   if (int rc = clips_prepare(pl, xy, N, smooth, s2, l.x, xy_s, st)) return rc;   // (x: rewritten by the resampling)
   if (int rc = spline_run(sl, sp, xy_s, clip_off_dev, S, N, R, s2, l.x, xy_r, off_out_dev, info, st)) return rc;
-  if (int rc = clips_index(pr, RN, st)) return rc;
-  for (int64_t s = 0; s < S; ++s)
-    if (int rc = lift_forward(m, l.x, l.y, off_r[s], off_r[s + 1], stream)) return rc;
-  if (!v) return clips_finish(pr, l.y, RN, xy_r, s3, poses, src, st);
-  if (int rc = lift_filter_run(v, K, l.y, off_out_dev, S, RN, eps, ctr, eps_row0, nullptr, nullptr, l.ref, ref_var, stream))
-    return rc;
-  const int rc = clips_finish(pr, l.ref, RN, xy_r, s3, poses, src, st);
-  if (rc || !poses_unfiltered) return rc;
-  return clips_finish(pr, l.y, RN, xy_r, s3, poses_unfiltered, src_unfiltered, st);
+  if (int rc = clips_index(pr.g, RN, st)) return rc;
+  return lift_batch_tail(m, f, pr, l, off_r.data(), RN, xy_r, {mean3, std3, use3, U3, cache_on_fail}, poses, src, stream);
 }

@@ -541,6 +541,40 @@ def export_bvh_clips(out_dir, names, frame_numbers, skeletons, fps=30.0):
             for name, fn, sk in zip(names, frame_numbers, skeletons)]
 
 
+def _check_resample(resample):
+    R = int(resample)
+    if R != resample or not 1 <= R <= 16:
+        raise ValueError("resample must be a whole number in 1..16 (the reference's multiplier 1 / resample)")
+    return R
+
+
+class _RowBuffers:
+    """Pinned (h) and device (d) tensors in pairs under the keys xy out src out_u src_u var (one row per
+    frame), info (one per clip) and off (the clip offsets), plus a 256-byte aligned workspace.  Each
+    grows on demand and never shrinks: a call that needs no more than an earlier one reallocates
+    nothing (a captured graph holds the addresses: size them with one eager call of the same kind
+    before capturing)."""
+
+    def __init__(self, torch, dev, out_size, h=None, d=None):
+        self.torch, self.dev, self.h, self.d = torch, dev, dict(h or {}), dict(d or {})
+        f64, i32 = torch.float64, torch.int32
+        self.kinds = dict(xy=((36,), f64), out=((96,), f64), src=((), i32), out_u=((96,), f64), src_u=((), i32),
+                          var=((out_size,), torch.float32), info=((36, 5), i32), off=((), torch.int64))
+        self.work, self.work_ptr, self.work_bytes = None, 0, 0
+
+    def need(self, keys, rows, work_bytes=0):
+        torch = self.torch
+        with torch.cuda.device(self.dev):
+            for k in keys:
+                if k not in self.d or self.d[k].shape[0] < rows:
+                    shape, dt = (rows,) + self.kinds[k][0], self.kinds[k][1]
+                    self.h[k] = torch.empty(shape, dtype=dt, pin_memory=True)
+                    self.d[k] = torch.empty(shape, dtype=dt, device=self.dev)
+            if work_bytes > self.work_bytes:
+                self.work, self.work_ptr = _aligned_workspace(torch, work_bytes, self.dev)
+                self.work_bytes = work_bytes
+
+
 class ClipLifter(_Lifter):
     """Lift whole OpenPose clips of up to `max_frames` frames with a float32 LinearModel: pinned
     rows in, ONE p3d_clip_lift (smoothing, mapping, forward tiles, post-processing), pinned rows
@@ -571,13 +605,22 @@ class ClipLifter(_Lifter):
             self.dsrc = torch.empty((n,), dtype=torch.int32, device=dev)
             self.work_bytes = int(_p3d.lib().p3d_clip_lift_workspace(n, model.input_size, model.output_size))
             self.work, self.work_ptr = _aligned_workspace(torch, self.work_bytes, dev)
-        # the batched call's offsets, workspace and optional outputs (set_offsets, _clips_buffers)
-        self._off, self._clips, self.hoff, self.doff = None, None, None, None
-        self.cwork, self.cwork_ptr, self.cwork_bytes = None, 0, 0
-        self.hout_u, self.hsrc_u, self.dout_u, self.dsrc_u, self.hvar, self.dvar = (None,) * 6
+        # the batched calls' rows, offsets and workspaces: the rows as given (the single clip's rows among
+        # them) and the resampled rows
+        self.rows = _RowBuffers(torch, dev, model.output_size, dict(xy=self.hxy, out=self.hout, src=self.hsrc),
+                                dict(xy=self.dxy, out=self.dout, src=self.dsrc))
+        self.resampled = _RowBuffers(torch, dev, model.output_size)
+        self._off, self._clips = None, None                  # the offsets of the last set_offsets; the last batched lift
         self._last_off, self._skel = None, None              # the last lift's clip offsets; skeleton()'s buffers
         self._last_rows = None                               # the last lift's device rows where not dout / dsrc (resampled)
-        self._rs = None                                      # the resampled lift's buffers (_resample_buffers)
+
+    # the batched call's optional rows, offsets and workspace under the names they had as attributes
+    dout_u = property(lambda self: self.rows.d.get("out_u"))
+    dsrc_u = property(lambda self: self.rows.d.get("src_u"))
+    dvar = property(lambda self: self.rows.d.get("var"))
+    doff = property(lambda self: self.rows.d.get("off"))
+    cwork_ptr = property(lambda self: self.rows.work_ptr)
+    cwork_bytes = property(lambda self: self.rows.work_bytes)
 
     def lift_device(self, n, smooth=True):
         """p3d_clip_lift of the first n rows of self.din into self.dxy / dout / dsrc (current stream)."""
@@ -610,7 +653,7 @@ class ClipLifter(_Lifter):
             raise ValueError("the last batched lift ran without a filter")
         off = lift_layout(int(_p3d.lib().p3d_clips_workspace(N, S)), N, self.model.input_size, self.model.output_size,
                           filtered)[1 + area]
-        return _p3d.device_view(self.cwork_ptr + off, (N, self.model.output_size), self.model.device.index)
+        return _p3d.device_view(self.rows.work_ptr + off, (N, self.model.output_size), self.model.device.index)
 
     def refined_rows(self):
         """View of the filter's refined rows [N, output_size] float32 of the last batched lift."""
@@ -629,121 +672,22 @@ class ClipLifter(_Lifter):
             raise ValueError("clip offsets must start at 0, every clip must have a frame, and at most "
                              "max_frames = %d frames in all" % self.max_frames)
         S = off.shape[0] - 1
-        if self.hoff is None or self.hoff.shape[0] < S + 1:
-            with torch.cuda.device(self.model.device):
-                self.hoff = torch.empty((S + 1,), dtype=torch.int64, pin_memory=True)
-                self.doff = torch.empty((S + 1,), dtype=torch.int64, device=self.model.device)
-        self.hoff.numpy()[:S + 1] = off
+        self.rows.need(("off",), S + 1)
+        self.rows.h["off"].numpy()[:S + 1] = off
         with torch.cuda.device(self.model.device):
-            self.doff[:S + 1].copy_(self.hoff[:S + 1], non_blocking=True)
+            self.doff[:S + 1].copy_(self.rows.h["off"][:S + 1], non_blocking=True)
         self._off = off
         return S, int(off[-1])
 
-    def _clips_buffers(self, S, filtered, unfiltered, variance):
-        """The batched call's workspace and optional outputs, grown on demand (a captured graph
-        holds the addresses: size them with one eager call of the same kind before capturing)."""
-        import _p3d
-        torch, dev, n = self.torch, self.model.device, self.max_frames
-        need = int(_p3d.lib().p3d_clips_lift_workspace(n, min(S, n), self.model.input_size, self.model.output_size,
-                                                       int(filtered)))
-        with torch.cuda.device(dev):
-            if self.cwork is None or need > self.cwork_bytes:
-                self.cwork, self.cwork_ptr = _aligned_workspace(torch, need, dev)
-                self.cwork_bytes = need
-            if unfiltered and self.dout_u is None:
-                self.hout_u = torch.empty((n, 96), dtype=torch.float64, pin_memory=True)
-                self.hsrc_u = torch.empty((n,), dtype=torch.int32, pin_memory=True)
-                self.dout_u = torch.empty((n, 96), dtype=torch.float64, device=dev)
-                self.dsrc_u = torch.empty((n,), dtype=torch.int32, device=dev)
-            if variance and self.dvar is None:
-                self.hvar = torch.empty((n, self.model.output_size), dtype=torch.float32, pin_memory=True)
-                self.dvar = torch.empty((n, self.model.output_size), dtype=torch.float32, device=dev)
-
-    def lift_clips_device(self, smooth=True, vae=None, samples=None, eps=None, ctr=0, eps_row0=0, unfiltered=False):
-        """ONE p3d_clips_lift of the rows self.din[:N] under the offsets of the last set_offsets, into
-        self.dxy / dout / dsrc (and dout_u / dsrc_u, dvar), on the current stream; capturable.  vae:
-        a models.VAE sequence filter run between the forward and the post-processing; samples=K:
-        the mean of K draws; eps: a device tensor [N, latent] ([K, N, latent]) or None for the
-        library's stream at (ctr, eps_row0 + row)."""
+    def _batch_args(self, b, resample, smooth, vae, samples, eps, ctr, eps_row0, unfiltered):
+        """What the two batched device calls share: the checks of their arguments (eps over R N rows),
+        the rows and the workspace of b (a _RowBuffers) sized for the call, and the arguments up to the
+        workspace that both library calls take -> (S, N, R, K, arguments)."""
         import _p3d
         if self._off is None:
             raise ValueError("set_offsets first")
-        S, N = self._off.shape[0] - 1, int(self._off[-1])
-        K = 0
-        if vae is None:
-            if samples is not None or eps is not None or unfiltered:
-                raise ValueError("samples, eps and unfiltered need a filter (vae=...)")
-        else:
-            K = _check_filter(vae, samples, self.model.output_size, "lift_clips")
-            if eps is not None and (tuple(eps.shape) != ((K, N, vae.latent_dim) if K else (N, vae.latent_dim))
-                                    or eps.dtype != self.torch.float32 or not eps.is_cuda or not eps.is_contiguous()):
-                raise ValueError("eps: expected a contiguous float32 device tensor %s"
-                                 % (((K, N, vae.latent_dim) if K else (N, vae.latent_dim)),))
-        self._clips_buffers(S, vae is not None, unfiltered, K > 0)
-        p = _p3d.ptr
-        _p3d.check(_p3d.lib().p3d_clips_lift(
-            self.model._h, None if vae is None else vae._h, K, p(eps), int(ctr), int(eps_row0),
-            p(self.din), self._off.ctypes.data, p(self.doff), S, N, int(bool(smooth)),
-            p(self.m2), p(self.s2), p(self.u2), self.u2.numel(), p(self.m3), p(self.s3), p(self.u3), self.u3.numel(), 96,
-            int(self.cache_on_fail), p(self.dxy), p(self.dout), p(self.dsrc),
-            p(self.dout_u) if unfiltered else None, p(self.dsrc_u) if unfiltered else None,
-            p(self.dvar) if K else None, self.cwork_ptr, self.cwork_bytes, self.model.stream()), "p3d_clips_lift")
-        self._clips = (S, N, vae is not None)
-        self._last_off, self._last_rows = self._off, None
-
-    # ------------------------------------------------------------------ spline-resampled clips
-    def _resample_buffers(self, S, N, R, filtered, unfiltered, variance):
-        """The resampled call's workspace and its R N output rows, grown on demand (as _clips_buffers: a
-        captured graph holds the addresses)."""
-        import _p3d
-        torch, dev, rows = self.torch, self.model.device, R * N
-        need = int(_p3d.lib().p3d_clips_lift_resampled_workspace(N, S, R, self.model.input_size, self.model.output_size,
-                                                                 int(filtered)))
-        rs = self._rs or dict(rows=0, S=0, work_bytes=0, unf=False, var=False)
-        with torch.cuda.device(dev):
-            if need > rs["work_bytes"]:
-                rs["work"], rs["work_ptr"] = _aligned_workspace(torch, need, dev)
-                rs["work_bytes"] = need
-            if rows > rs["rows"] or (unfiltered and not rs["unf"]) or (variance and not rs["var"]):
-                rows = max(rows, rs["rows"])
-                f64, i32 = torch.float64, torch.int32
-                pair = lambda shape, dt: (torch.empty(shape, dtype=dt, pin_memory=True),   # noqa: E731
-                                          torch.empty(shape, dtype=dt, device=dev))
-                rs["hxy"], rs["dxy"] = pair((rows, 36), f64)
-                rs["hout"], rs["dout"] = pair((rows, 96), f64)
-                rs["hsrc"], rs["dsrc"] = pair((rows,), i32)
-                if unfiltered or rs["unf"]:
-                    rs["hout_u"], rs["dout_u"] = pair((rows, 96), f64)
-                    rs["hsrc_u"], rs["dsrc_u"] = pair((rows,), i32)
-                    rs["unf"] = True
-                if variance or rs["var"]:
-                    rs["hvar"], rs["dvar"] = pair((rows, self.model.output_size), torch.float32)
-                    rs["var"] = True
-                rs["rows"] = rows
-            if S > rs["S"]:
-                rs["hinfo"] = torch.empty((S, 36, 5), dtype=torch.int32, pin_memory=True)
-                rs["dinfo"] = torch.empty((S, 36, 5), dtype=torch.int32, device=dev)
-                rs["doff"] = torch.empty((S + 1,), dtype=torch.int64, device=dev)
-                rs["S"] = S
-        self._rs = rs
-        return rs
-
-    def lift_clips_resampled_device(self, resample, smooth=True, vae=None, samples=None, eps=None, ctr=0, eps_row0=0,
-                                    unfiltered=False):
-        """ONE p3d_clips_lift_resampled of the rows self.din[:N] under the offsets of the last set_offsets:
-        smoothing into self.dxy, the spline resampling (the reference's --interpolation --multiplier
-        1 / resample) into the R N rows of self._rs['dxy'], and the lift of those rows into
-        self._rs['dout'] / ['dsrc'] (['dout_u'] / ['dsrc_u'], ['dvar']); ['dinfo'] [S, 36, 5] is the
-        fits' record and ['doff'] the resampled clips' offsets.  On the current stream; capturable.
-        eps rows count over the R N resampled rows."""
-        import _p3d
-        if self._off is None:
-            raise ValueError("set_offsets first")
-        R = int(resample)
-        if R != resample or not 1 <= R <= 16:
-            raise ValueError("resample must be a whole number in 1..16 (the reference's multiplier 1 / resample)")
-        S, N = self._off.shape[0] - 1, int(self._off[-1])
-        K = 0
+        R = 1 if resample is None else _check_resample(resample)
+        S, N, K = self._off.shape[0] - 1, int(self._off[-1]), 0
         if vae is None:
             if samples is not None or eps is not None or unfiltered:
                 raise ValueError("samples, eps and unfiltered need a filter (vae=...)")
@@ -753,17 +697,50 @@ class ClipLifter(_Lifter):
             if eps is not None and (tuple(eps.shape) != want or eps.dtype != self.torch.float32 or not eps.is_cuda
                                     or not eps.is_contiguous()):
                 raise ValueError("eps: expected a contiguous float32 device tensor %s" % (want,))
-        rs = self._resample_buffers(S, N, R, vae is not None, unfiltered, K > 0)
-        p = _p3d.ptr
-        _p3d.check(_p3d.lib().p3d_clips_lift_resampled(
+        lib, n, sizes = _p3d.lib(), self.max_frames, (self.model.input_size, self.model.output_size, int(vae is not None))
+        keys = ("xy", "out", "src") + (("out_u", "src_u") if unfiltered else ()) + (("var",) if K else ())
+        if resample is None:                                 # (the rows as given: sized once, for max_frames)
+            b.need(keys, n, int(lib.p3d_clips_lift_workspace(n, min(S, n), *sizes)))
+        else:
+            b.need(keys, R * N, int(lib.p3d_clips_lift_resampled_workspace(N, S, R, *sizes)))
+            b.need(("info",), S)
+            b.need(("off",), S + 1)
+        p, d = _p3d.ptr, b.d
+        return S, N, R, K, (
             self.model._h, None if vae is None else vae._h, K, p(eps), int(ctr), int(eps_row0),
             p(self.din), self._off.ctypes.data, p(self.doff), S, N, int(bool(smooth)),
             p(self.m2), p(self.s2), p(self.u2), self.u2.numel(), p(self.m3), p(self.s3), p(self.u3), self.u3.numel(), 96,
-            int(self.cache_on_fail), p(self.dxy), p(rs["dout"]), p(rs["dsrc"]),
-            p(rs["dout_u"]) if unfiltered else None, p(rs["dsrc_u"]) if unfiltered else None,
-            p(rs["dvar"]) if K else None, R, p(rs["dxy"]), p(rs["doff"]), p(rs["dinfo"]),
-            rs["work_ptr"], rs["work_bytes"], self.model.stream()), "p3d_clips_lift_resampled")
-        self._last_off, self._last_rows = self._off * R, (rs["dout"], rs["dsrc"])
+            int(self.cache_on_fail), p(self.dxy), p(d["out"]), p(d["src"]),
+            p(d["out_u"]) if unfiltered else None, p(d["src_u"]) if unfiltered else None, p(d["var"]) if K else None)
+
+    def lift_clips_device(self, smooth=True, vae=None, samples=None, eps=None, ctr=0, eps_row0=0, unfiltered=False):
+        """ONE p3d_clips_lift of the rows self.din[:N] under the offsets of the last set_offsets, into
+        self.dxy / dout / dsrc (and dout_u / dsrc_u, dvar), on the current stream; capturable.  vae:
+        a models.VAE sequence filter run between the forward and the post-processing; samples=K:
+        the mean of K draws; eps: a device tensor [N, latent] ([K, N, latent]) or None for the
+        library's stream at (ctr, eps_row0 + row)."""
+        import _p3d
+        b = self.rows
+        S, N, _, _, args = self._batch_args(b, None, smooth, vae, samples, eps, ctr, eps_row0, unfiltered)
+        _p3d.check(_p3d.lib().p3d_clips_lift(*args, b.work_ptr, b.work_bytes, self.model.stream()), "p3d_clips_lift")
+        self._clips = (S, N, vae is not None)
+        self._last_off, self._last_rows = self._off, None
+
+    def lift_clips_resampled_device(self, resample, smooth=True, vae=None, samples=None, eps=None, ctr=0, eps_row0=0,
+                                    unfiltered=False):
+        """ONE p3d_clips_lift_resampled of the rows self.din[:N] under the offsets of the last set_offsets:
+        smoothing into self.dxy, the spline resampling (the reference's --interpolation --multiplier
+        1 / resample) into the R N rows of self.resampled.d['xy'], and the lift of those rows into
+        its ['out'] / ['src'] (['out_u'] / ['src_u'], ['var']); ['info'] [S, 36, 5] is the fits' record
+        and ['off'] the resampled clips' offsets.  On the current stream; capturable.  eps rows count
+        over the R N resampled rows."""
+        import _p3d
+        b, p = self.resampled, _p3d.ptr
+        _, _, R, _, args = self._batch_args(b, resample, smooth, vae, samples, eps, ctr, eps_row0, unfiltered)
+        _p3d.check(_p3d.lib().p3d_clips_lift_resampled(
+            *args, R, p(b.d["xy"]), p(b.d["off"]), p(b.d["info"]), b.work_ptr, b.work_bytes, self.model.stream()),
+            "p3d_clips_lift_resampled")
+        self._last_off, self._last_rows = self._off * R, (b.d["out"], b.d["src"])
 
     def skeleton(self, lengths=None):
         """The rigid skeleton of the last lift_clip / lift_clips, from its device rows (dout, dsrc, the
@@ -814,9 +791,7 @@ class ClipLifter(_Lifter):
             raise ValueError("%d frames in all, max_frames is %d" % (N, self.max_frames))
         R = 1
         if resample is not None:
-            R = int(resample)
-            if R != resample or not 1 <= R <= 16:
-                raise ValueError("resample must be a whole number in 1..16 (the reference's multiplier 1 / resample)")
+            R = _check_resample(resample)
             if min(r.shape[0] for r in rows) < 4:
                 raise ValueError("need more frames, min 4 frames for a cubic spline")
             if R * N > 1 << 20:
@@ -839,29 +814,27 @@ class ClipLifter(_Lifter):
             self.din[:N_in].copy_(self.hin[:N_in], non_blocking=True)
             if resample is None:
                 self.lift_clips_device(smooth, vae, samples, eps, ctr or 0, 0, unfiltered)
-                b = dict(hxy=self.hxy, dxy=self.dxy, hout=self.hout, dout=self.dout, hsrc=self.hsrc, dsrc=self.dsrc,
-                         hout_u=self.hout_u, dout_u=self.dout_u, hsrc_u=self.hsrc_u, dsrc_u=self.dsrc_u,
-                         hvar=self.hvar, dvar=self.dvar)
+                h, d = self.rows.h, self.rows.d
             else:
                 self.lift_clips_resampled_device(R, smooth, vae, samples, eps, ctr or 0, 0, unfiltered)
-                b = self._rs
-                b["hinfo"][:len(rows)].copy_(b["dinfo"][:len(rows)], non_blocking=True)
+                h, d = self.resampled.h, self.resampled.d
+                h["info"][:len(rows)].copy_(d["info"][:len(rows)], non_blocking=True)
             keys = ["xy", "out", "src"] + (["out_u", "src_u"] if unfiltered else []) + (["var"] if K else [])
             for k in keys:
-                b["h" + k][:N].copy_(b["d" + k][:N], non_blocking=True)
+                h[k][:N].copy_(d[k][:N], non_blocking=True)
             torch.cuda.current_stream(self.model.device).synchronize()
         self.model.check_errors()
         first = np.repeat(off[:-1], np.diff(off))            # every row's clip start: 'src' counts from it (-1 stays)
         local = lambda t: np.where(t.numpy()[:N] >= 0, t.numpy()[:N] - first, -1).astype(np.int32)   # noqa: E731
-        views = [("poses", b["hout"].numpy()), ("xy_s", b["hxy"].numpy()), ("src", local(b["hsrc"]))]
+        views = [("poses", h["out"].numpy()), ("xy_s", h["xy"].numpy()), ("src", local(h["src"]))]
         if unfiltered:
-            views += [("poses_unfiltered", b["hout_u"].numpy()), ("src_unfiltered", local(b["hsrc_u"]))]
+            views += [("poses_unfiltered", h["out_u"].numpy()), ("src_unfiltered", local(h["src_u"]))]
         if K:
-            views.append(("ref_var", b["hvar"].numpy()))
+            views.append(("ref_var", h["var"].numpy()))
         res = self._results(off.tolist(), views)
         if resample is not None:
             for s, r in enumerate(res):
-                r["spline_info"] = b["hinfo"].numpy()[s].copy()
+                r["spline_info"] = h["info"].numpy()[s].copy()
         return res
 
     def lift_clip(self, xy, smooth=True, resample=None):

@@ -39,12 +39,13 @@ def test_every_refusal_of_the_parent_reproduces(pairs):
 def test_the_table_is_what_it_says(pairs):
     want, _, E = pairs
     by = {r["id"]: r["msg"] for r in want}
-    assert len(want) >= 120 and all(r["rc"] == E for r in want)
+    assert len(want) >= 200 and all(r["rc"] == E for r in want)
     for r in want:                                       # every message names the call that was made
         assert r["msg"].startswith("p3d_" + r["id"].split("/")[0] + ": "), r
     fns = {r["id"].split("/")[0] for r in want}
     assert fns == {"clip_prepare", "clip_finish", "clip_lift", "clips_prepare", "clips_finish", "clips_lift",
-                   "live_prepare", "live_finish", "live_push", "vae_seq_filter", "vae_seq_filter_mc"}
+                   "live_prepare", "live_finish", "live_push", "vae_seq_filter", "vae_seq_filter_mc",
+                   "clips_lift_resampled", "skel_lengths", "skel_pose", "clips_resample"}
     # the two-fault rows the shared stage could most easily turn round
     assert by["clips_lift/null_model_null_statistics"].endswith("null model")            # model first ...
     assert by["live_push/null_statistics"].endswith("null statistics")        # ... and model last
@@ -65,3 +66,19 @@ def test_the_table_is_what_it_says(pairs):
     assert "need a filter" in by["live_push/ref_var_without_filter"]
     assert "min 9 frames" in by["clip_prepare/smooth_2_frames_null_work"]
     assert "min 9 frames" in by["clips_prepare/smooth_clip_of_8_null_work"]
+    # the calls over clip offsets that take no handle: one check of the offsets behind all three
+    for fn in ("skel_lengths", "skel_pose", "clips_resample"):
+        assert by[fn + "/null_argument_bad_N"].endswith("null argument")
+        assert by[fn + "/null_offsets_bad_S"].endswith("null clip offsets")
+        assert by[fn + "/bad_S_bad_offsets"].endswith("S must be in 1..N clips")
+        assert by[fn + "/empty_then_decreasing"].endswith("clip 0 is empty")
+        assert "must not decrease (clip 1)" in by[fn + "/decreasing_then_empty"]
+        assert by[fn + "/past_the_end_then_decreasing"].endswith("clip offsets must end at N")
+    assert by["skel_lengths/misaligned_work_small"].endswith("null or misaligned workspace")
+    assert by["skel_pose/no_outputs_null_offsets"].endswith("null outputs: ask for at least one")
+    assert by["clips_resample/R0_clip_of_3"].endswith("R must be in 1..16")
+    assert "min 4 frames" in by["clips_resample/clip_of_3_bad_U2"]
+    assert by["clips_resample/bad_U2_alias"].endswith("U2 must be in 1..64")
+    assert by["clips_resample/alias_null_work"].endswith("xy_r must not alias xy_s")
+    assert by["clips_resample/R17_too_many_rows"].endswith("R must be in 1..16")
+    assert "R * N must be at most" in by["clips_resample/too_many_rows_long_clip"]

@@ -5,8 +5,8 @@ has to keep (tests/test_lift_errors.py).  No call reaches a launch, so this runs
 
     python tools/record_lift_errors.py PARENT/libp3d.so            # writes the fixture
     python tools/record_lift_errors.py PARENT/libp3d.so --check    # compares, writes nothing
-    python tools/record_lift_errors.py PARENT/libp3d.so --gpu      # on a GPU: the rows behind a live filter
-                                                                   # (tests/test_gpu_lift_errors.py) as well
+    python tools/record_lift_errors.py PARENT/libp3d.so --gpu      # on a GPU: the rows behind a live filter and
+                                                                   # behind a live model (tests/test_gpu_lift_errors.py) as well
 """
 import json
 import os
@@ -47,6 +47,11 @@ def main(argv):
         if late:
             raise SystemExit("not refused as a bad argument: %r" % late[:3])
         write(test_gpu_lift_errors.GOLD, rows)
+        rows = test_gpu_lift_errors.lift_handle_rows()
+        late = [r for r in rows if r["rc"] != _p3d.P3D_ERR_ARG]
+        if late:
+            raise SystemExit("not refused as a bad argument: %r" % late[:3])
+        write(test_gpu_lift_errors.GOLD_LIFT, rows)
     return 0
 
 

@@ -100,7 +100,7 @@ def main(argv=None):
         cl.din[:N].copy_(cl.hin[:N])
         t_lift = timed(torch, lambda: cl.lift_clips_device(True), f.iters)
         t_res = timed(torch, lambda: cl.lift_clips_resampled_device(R, True), f.iters)
-        rs, p, lib = cl._rs, _p3d.ptr, _p3d.lib()
+        rs, p, lib = cl.resampled.d, _p3d.ptr, _p3d.lib()
         nb = int(lib.p3d_clips_resample_workspace(N, S, R))
         work = torch.empty((nb // 8 + 32,), dtype=torch.float64, device="cuda")
         wp = (work.data_ptr() + 255) // 256 * 256
@@ -108,10 +108,10 @@ def main(argv=None):
 
         def alone():
             _p3d.check(lib.p3d_clips_resample(p(cl.dxy), cl._off.ctypes.data, p(cl.doff), S, N, R, p(cl.m2), p(cl.s2), p(cl.u2),
-                                              cl.u2.numel(), p(x), p(rs["dxy"]), p(rs["doff"]), p(rs["dinfo"]), wp, nb,
+                                              cl.u2.numel(), p(x), p(rs["xy"]), p(rs["off"]), p(rs["info"]), wp, nb,
                                               model.stream()), "p3d_clips_resample")
         t_alone = timed(torch, alone, f.iters)
-        info = rs["dinfo"][:S].cpu().numpy().reshape(-1, 5)
+        info = rs["info"][:S].cpu().numpy().reshape(-1, 5)
         print(json.dumps(dict(clips=S, frames=300, R=R, curves=36 * S, p3d_clips_lift_ms=t_lift,
                               p3d_clips_lift_resampled_ms=t_res, p3d_clips_resample_ms=t_alone,
                               resample_ms_per_curve=t_alone / (36 * S), workspace_MiB=nb / 2 ** 20,
