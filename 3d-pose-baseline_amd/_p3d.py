@@ -159,6 +159,11 @@ SIGNATURES = [
                                            c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
                                            c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    ("p3d_root_trajectory_workspace", c_int64, [c_int64, c_int32]),
+    ("p3d_root_trajectory_rows", c_int32, []),
+    ("p3d_root_trajectory", c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                      c_double, c_double, c_double, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_int64, c_void_p]),
     ("p3d_moments_workspace", c_int64, [c_int64, c_int32]),
     ("p3d_moments", c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     ("p3d_crc32c", c_uint32, [c_void_p, c_int64, c_uint32]),

@@ -25,6 +25,7 @@
 #include "p3d_live.h"
 #include "p3d_skel.h"
 #include "p3d_spline.h"
+#include "p3d_traj.h"
 #include "p3d_serve.h"
 #include "p3d_serve6.h"
 #include "p3d_serve_plan.h"
@@ -69,5 +70,7 @@
 #include "p3d_skel_host.h"
 // Spline-resampled clips: the fit, the samples and the lift over them (kernels in p3d_spline.h)
 #include "p3d_spline_host.h"
+// The root trajectory of lifted rows: the pinhole solve per frame and its windowed mean (kernels in p3d_traj.h)
+#include "p3d_traj_host.h"
 
 #include "p3d_dp.h"

@@ -159,10 +159,15 @@ struct ClipMap {
   double mean[64], stdv[64];
 };
 
-__device__ __forceinline__ void clip_load_map(const ClipInArgs& a, ClipMap& mp) {
-  // H3.6M joint -> OpenPose joint (order = [15, 12, 25, 26, 27, 17, 18, 19, 1, 2, 3, 6, 7, 8])
+// H3.6M joint -> OpenPose joint (order = [15, 12, 25, 26, 27, 17, 18, 19, 1, 2, 3, 6, 7, 8]; -1: none).
+// The one statement of the table on the device (p3d_traj.h reads its 2D joints through it too).
+__device__ __forceinline__ signed char clip_openpose_of(int h) {
   static constexpr signed char inv[32] = {-1, 8, 9, 10, -1, -1, 11, 12, 13, -1, -1, -1, 1, -1, -1, 0,
                                           -1, 5, 6, 7, -1, -1, -1, -1, -1, 2, 3, 4, -1, -1, -1, -1};
+  return inv[h];
+}
+
+__device__ __forceinline__ void clip_load_map(const ClipInArgs& a, ClipMap& mp) {
   for (int u = threadIdx.x; u < a.U2; u += P3D_CLIP_THREADS) {
     const int d = a.use2[u];
     const bool ok = d >= 0 && d < P3D_CLIP_D2;
@@ -171,7 +176,7 @@ __device__ __forceinline__ void clip_load_map(const ClipInArgs& a, ClipMap& mp) 
     if (h == 0) { kind = 1; ja = 1; jb = 6; }                       // Hip
     else if (h == 14) { kind = 1; ja = 15; jb = 12; }               // Neck/Nose
     else if (h == 13) { kind = 2; ja = 15; jb = 12; }               // Thorax
-    const int ia = inv[ja], ib = jb >= 0 ? inv[jb] : -1;
+    const int ia = clip_openpose_of(ja), ib = jb >= 0 ? clip_openpose_of(jb) : -1;
     mp.kind[u] = ok ? kind : -1;
     mp.ca[u] = ia >= 0 ? 2 * ia + k : -1;
     mp.cb[u] = ib >= 0 ? 2 * ib + k : -1;

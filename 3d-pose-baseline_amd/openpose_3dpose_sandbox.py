@@ -30,8 +30,11 @@ between the forward and the post-processing, every clip a fresh sequence; ``--fi
 averages K posterior samples per frame; ``--export_unfiltered`` also writes
 ``3d_data_unfiltered.json``, the poses without the filter.  ``--export_bvh`` also writes
 ``skeleton.bvh`` beside ``3d_data.json`` (``ClipLifter.skeleton``: constant bone lengths per clip,
-one rotation per bone and frame; ``--bvh_fps`` its frame rate; the 17-joint models only).  Without
-these flags the driver does what it did before them.
+one rotation per bone and frame; ``--bvh_fps`` its frame rate; the 17-joint models only).
+``--root_trajectory --focal F --principal CX CY`` also writes ``trajectory.json``
+(``ClipLifter.trajectory``: the camera-frame root translation per frame that puts the lifted joints
+onto their 2D tracks; ``--trajectory_smooth H`` its mean window's half width) and makes
+it the root of ``skeleton.bvh``.  Without these flags the driver does what it did before them.
 """
 from __future__ import annotations
 
@@ -91,6 +94,18 @@ def write_bvh(flags, out_dir, frame_numbers, sk):
                          fps=flags.bvh_fps)
 
 
+def with_trajectory(sk, tr):
+    """A skeleton dict whose root is the trajectory (in the skeleton's coordinates), where there is one."""
+    return sk if tr is None else dict(sk, root=tr["root_skel"])
+
+
+def trajectory_of(flags, lifter):
+    """--root_trajectory: ClipLifter.trajectory of the last lift under the flags' camera, else None."""
+    if not flags.root_trajectory:
+        return None
+    return lifter.trajectory(flags.focal, flags.principal, flags.trajectory_smooth)
+
+
 def run_clips(flags):
     """--clips_root / --vae_filter / --spline_resample: one p3d_clips_lift (p3d_clips_lift_resampled) over every clip."""
     if flags.clips_root:
@@ -114,6 +129,9 @@ def run_clips(flags):
         if flags.spline_resample is not None:                 # the resampled frames, renumbered from 0 (:283-284)
             numbers = [np.arange(len(r["poses"]), dtype=np.int64) for r in results]
         skeletons = lifter.skeleton() if flags.export_bvh else None
+        trajs = trajectory_of(flags, lifter)
+        if skeletons and trajs:
+            skeletons = [with_trajectory(sk, tr) for sk, tr in zip(skeletons, trajs)]
         if vae is not None:
             vae.close()
         model.close()
@@ -124,11 +142,16 @@ def run_clips(flags):
             paths += (of.export_unfiltered(flags.out_dir, numbers[0], r["poses_unfiltered"]),)
         if skeletons:
             paths += (write_bvh(flags, flags.out_dir, numbers[0], skeletons[0]),)
+        if trajs:
+            paths += (of.export_trajectory(flags.out_dir, numbers[0], trajs[0]),)
     else:
         paths = of.export_maya_clips(flags.out_dir, names, numbers, results, unfiltered=flags.export_unfiltered)
         if skeletons:
             bvh = of.export_bvh_clips(flags.out_dir, names, numbers, skeletons, fps=flags.bvh_fps)
             paths = [q + (b,) for q, b in zip(paths, bvh)]
+        if trajs:
+            paths = [q + (of.export_trajectory(os.path.join(flags.out_dir, name), fn, tr),)
+                     for q, name, fn, tr in zip(paths, names, numbers, trajs)]
     logger.info("exported maya json under %s", flags.out_dir)
     logger.info("Done!")
     return paths
@@ -148,6 +171,7 @@ def run(flags):
         raise SystemExit("--filter_samples and --export_unfiltered need --vae_filter")
     if flags.export_bvh and flags.predict_14:
         raise SystemExit("--export_bvh needs the 17-joint model: the skeleton's bones are not defined for --predict_14")
+    p3.check_trajectory_flags(flags)
     if flags.clips_root or flags.vae_filter or flags.spline_resample is not None:
         return run_clips(flags)
     logger.info("start reading json files")
@@ -168,10 +192,14 @@ def run(flags):
         if held:
             logger.info("%d failed frames replaced by the last good one", held)
         sk = lifter.skeleton()[0] if flags.export_bvh else None
+        tr = trajectory_of(flags, lifter)
+        tr = tr[0] if tr else None
         model.close()
     paths = of.export_maya(flags.out_dir, frame_numbers, poses, xy_s)
     if sk is not None:
-        paths += (write_bvh(flags, flags.out_dir, frame_numbers, sk),)
+        paths += (write_bvh(flags, flags.out_dir, frame_numbers, with_trajectory(sk, tr)),)
+    if tr is not None:
+        paths += (of.export_trajectory(flags.out_dir, frame_numbers, tr),)
     for path in paths:
         logger.info("exported maya json to %s", path)
     logger.info("Done!")

@@ -541,6 +541,140 @@ def export_bvh_clips(out_dir, names, frame_numbers, skeletons, fps=30.0):
             for name, fn, sk in zip(names, frame_numbers, skeletons)]
 
 
+# --------------------------------------------------------------------------------------
+# the root trajectory of lifted rows: the pinhole solve per frame, its windowed mean
+# --------------------------------------------------------------------------------------
+
+TRAJ_MAX_HALF = 32
+
+
+def _check_camera(focal, center, smooth_half):
+    """(focal, cx, cy, h) as the library takes them; ValueError for what it would refuse."""
+    try:
+        f = float(focal)
+        cx, cy = (float(c) for c in center)
+    except (TypeError, ValueError):
+        raise ValueError("expected a focal length and a principal point (cx, cy) in pixels") from None
+    if not (np.isfinite(f) and f > 0):
+        raise ValueError("focal must be finite and > 0, got %r" % (focal,))
+    if not (np.isfinite(cx) and np.isfinite(cy)):
+        raise ValueError("the principal point must be finite, got %r" % (center,))
+    h = int(smooth_half)
+    if h != smooth_half or not 0 <= h <= TRAJ_MAX_HALF:
+        raise ValueError("smooth_half must be a whole number in 0..%d" % TRAJ_MAX_HALF)
+    return f, cx, cy, h
+
+
+class _TrajectoryBuffers:
+    """The device and pinned rows of p3d_root_trajectory, grown on demand (a captured graph holds the
+    addresses: size them with one eager call before capturing)."""
+
+    OUT = (("traj", (3,), "float64"), ("traj_raw", (3,), "float64"), ("resid", (), "float64"), ("valid", (), "int32"))
+
+    def __init__(self, torch, device):
+        self.torch, self.device = torch, device
+        self.rows, self.clips, self.work_bytes, self.work_ptr = 0, 0, 0, None
+
+    def _grow(self, N, S, h):
+        import _p3d
+        torch, dev = self.torch, self.device
+        with torch.cuda.device(dev):
+            if N > self.rows:
+                self.d = {k: torch.empty((N,) + shp, dtype=getattr(torch, dt), device=dev) for k, shp, dt in self.OUT}
+                self.h = {k: torch.empty((N,) + shp, dtype=getattr(torch, dt), pin_memory=True) for k, shp, dt in self.OUT}
+                self.rows = N
+            if S > self.clips:
+                self.hoff = torch.empty((S + 1,), dtype=torch.int64, pin_memory=True)
+                self.doff = torch.empty((S + 1,), dtype=torch.int64, device=dev)
+                self.clips = S
+            need = int(_p3d.lib().p3d_root_trajectory_workspace(N, h))
+            if need > self.work_bytes:
+                self.work, self.work_ptr = _aligned_workspace(torch, need, dev)
+                self.work_bytes = need
+
+    def run(self, dposes, dxy, dsrc, off, focal, center, smooth_half):
+        """The call on device rows dposes [>= N, 96] / dxy [>= N, 36] / dsrc [>= N] int32 or None under
+        the clip offsets `off` (int64 [S + 1]) -> one dict per clip."""
+        import _p3d
+        f, cx, cy, h = _check_camera(focal, center, smooth_half)
+        torch, lib, p = self.torch, _p3d.lib(), _p3d.ptr
+        off = np.ascontiguousarray(off, np.int64)
+        S, N = off.shape[0] - 1, int(off[-1])
+        self._grow(N, S, h)
+        with torch.cuda.device(self.device):
+            self.hoff.numpy()[:S + 1] = off
+            self.doff[:S + 1].copy_(self.hoff[:S + 1], non_blocking=True)
+            _p3d.check(lib.p3d_root_trajectory(p(dposes), p(dxy), p(dsrc), off.ctypes.data, p(self.doff), S, N, f, cx, cy,
+                                               h, *(p(self.d[k]) for k, _, _ in self.OUT), self.work_ptr, self.work_bytes,
+                                               _p3d.stream_handle()), "p3d_root_trajectory")
+            for k, _, _ in self.OUT:
+                self.h[k][:N].copy_(self.d[k][:N], non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+        out = _Lifter._results(off.tolist(), [(k, self.h[k].numpy()) for k, _, _ in self.OUT])
+        for r in out:
+            r["valid"] = r["valid"] != 0
+            # skeleton coordinates (X, Y, Z) = (ex, ez, -ey) with ex = camera x, ey = camera z, ez = -camera y
+            r["root_skel"] = r["traj"] * np.array([1.0, -1.0, -1.0]) + 0.0   # (no -0.0 in a BVH)
+            r["camera"] = dict(focal=f, center=[cx, cy], smooth_half=h)
+        return out
+
+
+def trajectory_rows(poses, xy_s, src, offsets, focal, center, smooth_half=0, device=None):
+    """The root trajectory of host rows: poses [N, 96] and xy_s [N, 36] float64 as the lifters return
+    them (a LiveLifter stream's collected rows, ``3d_data.json`` / ``2d_data.json`` read back), S clips
+    one after another under `offsets` [S + 1]; src [N]: each clip's 'src' as the lifters return it
+    (positions inside the clip, -1: zeros), concatenated, or None (every row its own).  focal and
+    center = (cx, cy) are the camera's, in the pixels of xy_s; smooth_half = h in 0..32 averages the
+    valid rows at most h frames away inside the clip.  Returns one dict per clip: 'traj' [n, 3] and
+    'traj_raw' [n, 3] (Tx, Ty, Tz in the camera's frame: x right, y down, z forward, the 3D
+    statistics' unit), 'resid' [n] (the reprojection residual, pixels), 'valid' [n] bool, 'root_skel'
+    [n, 3] = (Tx, -Ty, -Tz), the trajectory in the skeleton's coordinates (export_bvh's `root`), and
+    'camera'.  The solve takes the 3D rows to be in the camera's frame (a model trained with
+    --camera_frame) and the camera to be the video's; it cannot check either."""
+    import torch
+    poses = np.ascontiguousarray(poses, np.float64)
+    xy_s = np.ascontiguousarray(xy_s, np.float64)
+    off = np.asarray(offsets)
+    if poses.ndim != 2 or poses.shape[1] != 96 or poses.shape[0] < 1:
+        raise ValueError("expected poses [N >= 1, 96] (32 joints), got %s" % (poses.shape,))
+    if xy_s.shape != (poses.shape[0], 36):
+        raise ValueError("expected xy_s [%d, 36] (18 joints), got %s" % (poses.shape[0], xy_s.shape))
+    if off.ndim != 1 or off.shape[0] < 2 or not np.issubdtype(off.dtype, np.integer) or off[0] != 0 \
+            or (np.diff(off) <= 0).any() or off[-1] != poses.shape[0]:
+        raise ValueError("clip offsets must be integers [S + 1] that start at 0, give every clip a frame and end at N")
+    off = off.astype(np.int64)
+    _check_camera(focal, center, smooth_half)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    with torch.cuda.device(dev):
+        dsrc = None
+        if src is not None:
+            src = np.asarray(src)
+            if src.shape != (poses.shape[0],) or not np.issubdtype(src.dtype, np.integer):
+                raise ValueError("src: expected %d integers, got %s %s" % (poses.shape[0], src.dtype, src.shape))
+            if (src >= np.repeat(np.diff(off), np.diff(off))).any():
+                raise ValueError("src: a position past its clip's end")
+            first = np.repeat(off[:-1], np.diff(off))
+            dsrc = torch.from_numpy(np.where(src >= 0, src + first, -1).astype(np.int32)).to(dev)
+        return _TrajectoryBuffers(torch, dev).run(torch.from_numpy(poses).to(dev), torch.from_numpy(xy_s).to(dev), dsrc,
+                                                  off, focal, center, smooth_half)
+
+
+def export_trajectory(out_dir, frame_numbers, result):
+    """Write ``trajectory.json`` into `out_dir` from one clip's trajectory_rows / ClipLifter.trajectory
+    dict: {"trajectory": {frame: [Tx, Ty, Tz]}, "resid": [...], "valid": [...], "camera": {focal,
+    center, smooth_half}}.  Returns the path."""
+    traj, resid, valid = np.asarray(result["traj"], np.float64), np.asarray(result["resid"], np.float64), np.asarray(result["valid"])
+    n = len(frame_numbers)
+    if traj.shape != (n, 3) or resid.shape != (n,) or valid.shape != (n,) or n < 1:
+        raise ValueError("expected traj [N, 3], resid [N], valid [N] and N >= 1 frame numbers")
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, "trajectory.json")
+    with open(path, "w") as f:
+        json.dump({"trajectory": {int(frame): traj[i].tolist() for i, frame in enumerate(frame_numbers)},
+                   "resid": resid.tolist(), "valid": [bool(v) for v in valid], "camera": result["camera"]}, f)
+    return path
+
+
 def _check_resample(resample):
     R = int(resample)
     if R != resample or not 1 <= R <= 16:
@@ -613,6 +747,7 @@ class ClipLifter(_Lifter):
         self._off, self._clips = None, None                  # the offsets of the last set_offsets; the last batched lift
         self._last_off, self._skel = None, None              # the last lift's clip offsets; skeleton()'s buffers
         self._last_rows = None                               # the last lift's device rows where not dout / dsrc (resampled)
+        self._traj = None                                    # trajectory()'s buffers
 
     # the batched call's optional rows, offsets and workspace under the names they had as attributes
     dout_u = property(lambda self: self.rows.d.get("out_u"))
@@ -757,6 +892,23 @@ class ClipLifter(_Lifter):
             self._skel = _SkeletonBuffers(self.torch, self.model.device)
         dout, dsrc = self._last_rows or (self.dout, self.dsrc)
         return self._skel.run(dout, dsrc, self._last_off, lengths)
+
+    def trajectory(self, focal, center, smooth_half=0):
+        """The root trajectory of the last lift_clip / lift_clips (also with resample= and vae=), from its
+        device rows (the poses, the 2D rows the network saw, src, the clip offsets): p3d_root_trajectory,
+        no model involved and any joint count.  focal, center = (cx, cy): the camera's, in the pixels
+        of the keypoints; smooth_half: the window's half width in frames, 0..32.  Returns one dict per
+        clip (one for lift_clip): 'traj', 'traj_raw' [n, 3], 'resid' [n], 'valid' [n] bool, 'root_skel'
+        [n, 3], 'camera' -- see trajectory_rows, which says what the solve assumes."""
+        if self._last_off is None:
+            raise ValueError("no lift has run yet")
+        if self._traj is None:
+            self._traj = _TrajectoryBuffers(self.torch, self.model.device)
+        if self._last_rows is None:
+            dout, dsrc, dxy = self.dout, self.dsrc, self.dxy
+        else:                                                # (resampled: the rows the lifter saw are the resampled ones)
+            dout, dsrc, dxy = self._last_rows + (self.resampled.d["xy"],)
+        return self._traj.run(dout, dxy, dsrc, self._last_off, focal, center, smooth_half)
 
     def lift_clips(self, clips, smooth=True, vae=None, samples=None, eps=None, ctr=None, unfiltered=False,
                    resample=None):

@@ -82,6 +82,16 @@ def build_parser():
                    help="openpose front ends: also write skeleton.bvh (constant bone lengths, per-bone "
                         "rotations) beside 3d_data.json")
     p.add_argument("--bvh_fps", type=float, default=30.0, help="--export_bvh: frames per second of the BVH file")
+    p.add_argument("--root_trajectory", action='store_true', default=False,
+                   help="openpose front ends: also write trajectory.json, the camera-frame root translation per "
+                        "frame from the 2D tracks (needs --focal; a --camera_frame model); with --export_bvh it "
+                        "is the BVH's root")
+    p.add_argument("--focal", type=float, default=None, help="--root_trajectory: the video's focal length, pixels")
+    p.add_argument("--principal", type=float, nargs=2, default=None, metavar=("CX", "CY"),
+                   help="--root_trajectory: the video's principal point, pixels")
+    p.add_argument("--trajectory_smooth", type=int, default=4,
+                   help="--root_trajectory: half width in frames of the trajectory's mean window, 0..32 (4: the 2D "
+                        "median's reach)")
     p.add_argument("--sample_dir", type=str, default="",
                    help="--sample: directory that receives samples.npz, the rows the reference would "
                         "draw (empty: not written)")
@@ -89,6 +99,20 @@ def build_parser():
                    help="1: stage each epoch in HBM and train without per-step host round trips; "
                         "0: the reference's per-batch step() loop")
     return p
+
+
+def check_trajectory_flags(flags):
+    """--root_trajectory: the camera has no silent default.  Exits with what is missing."""
+    if not flags.root_trajectory:
+        return
+    if flags.focal is None or flags.principal is None:
+        raise SystemExit("--root_trajectory needs --focal F and --principal CX CY, the video's own camera in pixels; "
+                         "H3.6M's nominal camera, which the shipped statistics assume, is f ~ 1145 px with centre "
+                         "~ (512, 515) on a 1000 x 1002 image")
+    if not flags.focal > 0:
+        raise SystemExit("--focal must be > 0")
+    if not 0 <= flags.trajectory_smooth <= 32:
+        raise SystemExit("--trajectory_smooth must be in 0..32")
 
 
 FLAGS = build_parser().parse_args([])   # defaults; main() re-parses argv

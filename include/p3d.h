@@ -709,6 +709,55 @@ int p3d_clips_lift_resampled(p3d_model* m, struct p3d_vae* v /* or NULL */, int3
                              double* xy_r, int64_t* off_out_dev, int32_t* info /* or NULL */, void* work,
                              int64_t work_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * The ROOT TRAJECTORY of lifted rows: per frame the translation T = (Tx, Ty, Tz) in
+ * the camera's frame (x right, y down, z forward, the 3D statistics' unit) that puts the
+ * root-relative 3D joints of a `poses` row onto the 2D joints of an `xy_s` row under a pinhole
+ * camera (focal length `focal`, principal point (cx, cy), pixels), in closed form.  `poses` [N, 96]
+ * and `xy_s` [N, 36] float64 are rows as the clip, clips and live calls write them, S clips one after
+ * another under clip offsets as at p3d_skel_pose (host copy: validated; device copy: read by the
+ * kernels, clamped into [0, N]; no loads for it at S = 1); src [N] int32 is the clip calls' (row
+ * indices into the batch) or NULL (every row its own).  Row n with s = src[n] takes its 3D from
+ * poses[n] and its 2D from xy_s[s] (read clamped to N - 1); s < 0: T = 0, resid = 0, valid = 0.
+ *
+ * The 13 joints j of H3.6M {0,1,2,3,6,7,8,17,18,19,25,26,27} (hip, legs, arms), their 2D (u, v) the
+ * OpenPose joint of the clip calls' mapping, the hip's (RHip + LHip) / 2; with P = poses[n]:
+ *   x = P[3j] - P[0], z = P[3j+1] - P[1], y = P[2] - P[3j+2]   (camera frame, the export's offsets cancel)
+ *   a = (u - cx) / focal, b = (v - cy) / focal, p = a z - x, q = b z - y
+ *   am, bm, pm, qm = sum / 13; da = a - am, db = b - bm; D = sum(da da + db db), Nn = sum(da p + db q)
+ *   D < 1e-12 (the 2D joints coincide): T = 0, resid = 0, valid = 0.  Else valid = 1 and
+ *   Tz = -Nn / D, Tx = pm + am Tz, Ty = qm + bm Tz
+ *   resid = sqrt(sum(eu eu + ev ev) / 13), eu = focal ((x + Tx) / (z + Tz)) - (u - cx), ev alike (pixels).
+ * Every sum is one pairwise tree over 16 slots (13 joints and three +0.0), every operation float64
+ * and rounded on its own; a non-finite value follows the arithmetic (a NaN D is not below the bound).
+ * A joint behind the camera is not special: the residual shows it.
+ *
+ *   traj_raw [N, 3]  T;  resid [N];  valid [N] int32
+ *   traj     [N, 3]  smooth_half = h: the sum, in ascending frame order, of the valid raw rows at most
+ *                    h frames away inside the row's clip, divided by their number; zeros where the row
+ *                    itself is not valid.  h = 0: the raw rows, byte for byte.
+ * Each output may be NULL, not all.  `work`: p3d_root_trajectory_workspace(N, smooth_half) bytes of
+ * device memory, 8-byte aligned (0 bytes at h = 0: NULL is fine): where the raw rows and the flags
+ * stand when traj is asked for and they are not.  p3d_root_trajectory_rows(): the rows one solve
+ * workgroup owns.  The call needs no model, is asynchronous and capturable (the solve's launch and,
+ * with h > 0 and traj, the smoothing's behind it), and gives the same bits on every run; a clip
+ * inside a batch carries the bits of the call on that clip alone.  It cannot know whether the rows
+ * are in the camera's frame (a model trained with --camera_frame) or whether focal / cx / cy are the
+ * video's: the caller vouches for both.
+ *
+ * P3D_ERR_ARG ("p3d_root_trajectory: ...") without touching the GPU: a null poses, xy_s or offsets;
+ * all four outputs null; N or S outside 1 <= S <= N <= 2^20; offsets that do not start at 0,
+ * decrease, hold an empty clip or do not end at N; focal not finite or <= 0; cx or cy not finite;
+ * smooth_half outside 0 .. 32; with smooth_half > 0 a null, short or misaligned (8 bytes) workspace.
+ * ------------------------------------------------------------------------------------- */
+int64_t p3d_root_trajectory_workspace(int64_t N, int32_t smooth_half);
+int32_t p3d_root_trajectory_rows(void);
+int p3d_root_trajectory(const double* poses, const double* xy_s, const int32_t* src /* or NULL */,
+                        const int64_t* clip_off_host, const int64_t* clip_off_dev, int64_t S, int64_t N,
+                        double focal, double cx, double cy, int32_t smooth_half, double* traj, double* traj_raw,
+                        double* resid, int32_t* valid /* each may be NULL, not all */, void* work,
+                        int64_t work_bytes, void* stream);
+
 /* np.mean / np.std (population) over axis 0 of x [F, D], D <= 256 -- the statistics of
  * src/data_utils.py:210-211 (normalization_stats).  Deterministic two-level column sums;
  * `work` must hold p3d_moments_workspace(F, D) bytes of device memory. */
